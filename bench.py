@@ -16,9 +16,17 @@ xGMI, the default; gloo for plumbing runs of several ranks on one device).  The 
 `run()`, which takes the engine factory and the device, so tests/test_bench_dist.py drives the same
 code with a stand-in engine on CPU ranks.
 
-Beside the headline (rank 0, N = 1 only): the same workload at 64 utterances per call (`batch64`),
-the fp32-accurate split-bf16 GEMM mode, config C4 (wav2vec2-large, 20 steps, bf16) and config C5
-(a seeded TED-like length mix through the driver's ragged grouping).
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does what the headline needs and no more: set-up,
+W warm-up steps, K timed steps, the JSON line.  `--dump-outputs DIR` also writes what the last timed step
+returned to its caller (the greedy ids of every recorded SUTA step, `DIR/ids_step<r>.npy`, and the frame count,
+`DIR/frames.npy`) and, from one untimed repeat of that step, the logits the ids are the argmax of
+(`DIR/logits_step<r>.npy`); weights and utterances are seeded, so two builds run with the same arguments can be
+compared array for array.
+
+`--full` adds everything else to the line: the per-kernel HIP-event pass (roofline, time breakdown, front-end and
+attention figures), the same workload at 64 utterances per call (`batch64`), the fp32-accurate split-bf16 GEMM
+mode, the CPU baseline, config C4 (wav2vec2-large, 20 steps, bf16) and config C5 (a seeded TED-like length mix
+through the driver's ragged grouping); each has its `--no-...` switch.  C4, C5 and the CPU baseline need N = 1.
 """
 import argparse
 import json
@@ -211,19 +219,52 @@ def shard_start(rank, nbatches, batch, i):
 
 def timed_batches(eng, waves, first, count, S, hp, record, comm, dev):
     """`count` adapt calls on waves[first:first+count], bracketed by barrier + device sync on both sides;
-    returns (this rank's elapsed s, max over ranks)."""
+    returns (this rank's elapsed s, max over ranks, what the last call returned)."""
     def fence():
         comm.barrier()
         dev.sync()
         eng.sync()
+    last = None
     fence()
     t0 = time.perf_counter()
     for i in range(count):
-        eng.adapt(waves[first + i], S, hp, record=record, want_logits=False)
+        last = eng.adapt(waves[first + i], S, hp, record=record, want_logits=False)
     eng.sync()
     fence()
     el = time.perf_counter() - t0
-    return el, comm.max(el)
+    return el, comm.max(el), last
+
+
+def synth_batches(n, count, starts):
+    """synth.batch(n, count, start) for every start, the utterances generated on a thread pool (numpy's generators
+    and reductions release the GIL): a batch of 164 x 8 s takes about a second on one core."""
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max(1, min(16, len(os.sched_getaffinity(0))))) as pool:
+        for s in starts:
+            yield np.stack(list(pool.map(lambda i: synth.wave(n, i), range(s, s + count))))
+
+
+DUMP_LOGITS_BYTES = 56 << 20   # --dump-outputs: room for the logits (the whole dump stays under 64 MB)
+
+
+def dump_outputs(path, last, logits):
+    """--dump-outputs: what the last timed adapt call returned -- (None: the timed path asks for no logits,
+    {recorded step: greedy ids (B, T)}, T) -- as float32 .npy files (ids are below the vocabulary size, so exact),
+    and the logits those ids are the argmax of, {recorded step: (B, T, V)} from a repeat of that call (None: not
+    written).  Logits beyond DUMP_LOGITS_BYTES are cut to a seeded sample of the utterances, whose indices are
+    logits_utterances.npy."""
+    _, ids, frames = last
+    os.makedirs(path, exist_ok=True)
+    for r, a in ids.items():
+        np.save(os.path.join(path, f"ids_step{r:02d}.npy"), np.asarray(a, dtype=np.float32))
+    np.save(os.path.join(path, "frames.npy"), np.asarray([frames], dtype=np.float32))
+    if logits:
+        n = len(next(iter(logits.values())))
+        keep = max(1, min(n, DUMP_LOGITS_BYTES // max(1, sum(a[0].nbytes for a in logits.values()))))
+        rows = np.arange(n) if keep == n else np.sort(np.random.default_rng(20260415).choice(n, keep, replace=False))
+        np.save(os.path.join(path, "logits_utterances.npy"), rows.astype(np.float32))
+        for r, a in logits.items():
+            np.save(os.path.join(path, f"logits_step{r:02d}.npy"), np.asarray(a[rows], dtype=np.float32))
 
 
 def run(args, rank, world, comm, dev, make_engine):
@@ -237,17 +278,24 @@ def run(args, rank, world, comm, dev, make_engine):
     nbatches = args.warmup + args.steps
     # inputs resident in device memory before timing: distinct utterances per rank and batch
     starts = [shard_start(rank, nbatches, B, i) for i in range(nbatches)]
-    waves = [dev.put(synth.batch(N, B, start=s)) for s in starts]
+    waves = [dev.put(a) for a in synth_batches(N, B, starts)]
     dev.sync()
     for i in range(args.warmup):
         eng.adapt(waves[i], S, hp, record=RECORD, want_logits=False)
-    el_rank, el = timed_batches(eng, waves, args.warmup, args.steps, S, hp, RECORD, comm, dev)
+    el_rank, el, last = timed_batches(eng, waves, args.warmup, args.steps, S, hp, RECORD, comm, dev)
     rank_el = comm.gather(round(el_rank, 6))
     shards = comm.gather([starts[args.warmup], starts[-1] + B])   # timed utterances [first, end) per rank
+    if args.dump_outputs and rank == 0 and last is not None:
+        # the timed calls copy out ids alone (on seeded random weights one label nearly everywhere): the same call
+        # once more, untimed, with the logits it computed them from
+        logits, _, _ = eng.adapt(waves[-1], S, hp, record=RECORD)
+        dump_outputs(args.dump_outputs, last, logits)
+    # everything below the headline is --full's; each part keeps its own --no-... switch
+    per_kernel = args.full and not args.no_timing
     # roofline pass (outside the timed region): per-launch HIP events on the engine stream; this runs
     # the eager path (timing disables graph replay), so its batch time is reported separately
     timing, timing_el, tsteps = None, None, max(1, min(args.timing_steps, args.steps))
-    if not args.no_timing:
+    if per_kernel:
         eng.set_timing(True)
         comm.barrier()
         t1 = time.perf_counter()
@@ -328,19 +376,19 @@ def run(args, rank, world, comm, dev, make_engine):
             nf, nb = (S + 1) * layers * tsteps, S * layers * tsteps
             out["attention"] = {"launches": int(ax[1]), "ms": round(ax[0], 2),
                                 "tflops": round((nf * af + nb * ab) / (ax[0] / 1000) / 1e12, 3)}
-    if args.batch64 and B > 64 and args.steps >= 2:
+    if args.full and args.batch64 and B > 64 and args.steps >= 2:
         # the same workload at 64 utterances per call (the batch of rounds 1-2): round-over-round comparison
         w64 = [w[:64] for w in waves]
         eng.adapt(w64[0], S, hp, record=RECORD, want_logits=False)     # new layout: capture on the next call
         eng.adapt(w64[1], S, hp, record=RECORD, want_logits=False)
-        el64_rank, el64 = timed_batches(eng, w64, args.warmup, args.steps, S, hp, RECORD, comm, dev)
+        el64_rank, el64, _ = timed_batches(eng, w64, args.warmup, args.steps, S, hp, RECORD, comm, dev)
         out["batch64"] = {"value": round(64 * args.steps * world / el64, 4),
                           "ms_per_step": round(1000 * el64 / args.steps, 3), "batch": 64}
-    if args.also_split and args.precision == "fp32":
+    if args.full and args.also_split and args.precision == "fp32":
         # same workload with the fp32-accurate split-bf16 GEMMs (reported beside the headline)
         eng.set_precision("fp32-split-bf16")
         eng.adapt(waves[0], S, hp, record=RECORD, want_logits=False)
-        el2_rank, el2 = timed_batches(eng, waves, args.warmup, args.steps, S, hp, RECORD, comm, dev)
+        el2_rank, el2, _ = timed_batches(eng, waves, args.warmup, args.steps, S, hp, RECORD, comm, dev)
         split = {"precision": "fp32-split-bf16", "value": round(utts / el2, 4),
                  "ms_per_step": round(1000 * el2 / args.steps, 3)}
         if not args.no_timing:
@@ -356,10 +404,10 @@ def run(args, rank, world, comm, dev, make_engine):
                                  "note": "6 bf16 MFMA products per fp32 MAC: peak = 2500 TF bf16 dense / 6"}
         out["fp32_split_bf16"] = split
         eng.set_precision("fp32")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, N, S)
     eng.close()
-    if world == 1 and args.precision == "fp32" and dev.index is not None:
+    if args.full and world == 1 and args.precision == "fp32" and dev.index is not None:
         if args.c4:
             out["c4"] = bench_c4(args, dev.index)
         if args.c5:
@@ -546,6 +594,12 @@ def build_parser():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="collectives under torchrun: nccl = RCCL over xGMI (one GPU per rank); gloo = host "
                          "collectives, ranks may share a device (rank r uses GPU LOCAL_RANK mod device count)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: per-kernel timing pass (roofline), batch64, split-bf16 mode, CPU "
+                         "baseline, configs C4 and C5 (each with its --no-... switch); a plain run has none of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0: greedy ids, frame count) and the logits "
+                         "of an untimed repeat of it as DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-timing", action="store_true", help="skip the per-kernel HIP-event timing pass")
     ap.add_argument("--timing-steps", type=int, default=1,

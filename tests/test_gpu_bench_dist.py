@@ -21,7 +21,7 @@ def test_bench_two_gloo_ranks_on_one_gpu():
     B, steps, warmup = 4, 2, 1
     argv = [sys.executable, "-u", os.path.join(REPO, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
             "--batch", str(B), "--n-samples", "32000", "--steps", str(steps), "--warmup", str(warmup),
-            "--no-cpu-baseline", "--no-c4", "--no-c5", "--no-split", "--no-batch64"]
+            "--full", "--no-cpu-baseline", "--no-c4", "--no-c5", "--no-split", "--no-batch64"]
     procs = []
     for r in range(world):
         env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), LOCAL_WORLD_SIZE=str(world),

@@ -5,7 +5,7 @@ set -e
 export TMPDIR=/tmp
 O=gpurun_out/prof2
 mkdir -p $O
-B="python3 bench.py --steps 1 --warmup 0 --no-split --no-cpu-baseline --no-timing --no-c4"
+B="python3 bench.py --full --steps 1 --warmup 0 --no-split --no-cpu-baseline --no-timing --no-c4"
 C="python3 bench.py --only-c4 --steps 2 --no-timing --c4-batch 16"
 timeout -s KILL 170 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_c4b16_fetch -- $C > $O/pmc_c4b16_fetch.log 2>&1
 timeout -s KILL 170 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_c4b16_write -- $C > $O/pmc_c4b16_write.log 2>&1

@@ -2,7 +2,7 @@ set -e
 export TMPDIR=/tmp
 O=gpurun_out/prof2
 mkdir -p $O
-B="python3 bench.py --steps 1 --warmup 0 --no-split --no-cpu-baseline --no-timing --no-c4"
+B="python3 bench.py --full --steps 1 --warmup 0 --no-split --no-cpu-baseline --no-timing --no-c4"
 C="python3 bench.py --only-c4 --steps 2 --no-timing --c4-batch 16"
 timeout -k 10 300 python -u -m pytest tests/test_gpu_large_bf16.py -k planes -x -q --timeout 200 --timeout-method thread > $O/planes_test.log 2>&1
 timeout -s KILL 170 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT --output-format csv -d $O/pmc_sq -- $B > $O/pmc_sq.log 2>&1

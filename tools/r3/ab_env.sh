@@ -11,7 +11,7 @@ for v in "SUTA_HB_NS=2" "SUTA_HB_NS=5" "SUTA_HB_NS=6" "SUTA_HB8=1"; do
 env $v timeout -k 10 300 python bench.py --only-c4 --steps 2 > $O/c4_$v.$i.json 2> $O/c4_$v.$i.err
 done
 for g in 0 4 8; do
-SUTA_GEMM_ORDER=$g timeout -k 10 300 python bench.py --steps 3 --no-split --no-cpu-baseline --no-c4 > $O/c2_order$g.$i.json 2> $O/c2_order$g.$i.err
+SUTA_GEMM_ORDER=$g timeout -k 10 300 python bench.py --full --steps 3 --no-split --no-cpu-baseline --no-c4 > $O/c2_order$g.$i.json 2> $O/c2_order$g.$i.err
 done
 done
 echo done

@@ -10,6 +10,6 @@ for w in 4 8; do
 SUTA_FLASH_FWD_NW=$w timeout -k 10 300 python bench.py --only-c4 --steps 2 > $O/c4_nw$w.$i.json 2> $O/c4_nw$w.$i.err
 done
 done
-timeout -k 10 300 python bench.py --steps 3 --no-split --no-cpu-baseline --no-c4 > $O/c2.json 2> $O/c2.err
+timeout -k 10 300 python bench.py --full --steps 3 --no-split --no-cpu-baseline --no-c4 > $O/c2.json 2> $O/c2.err
 bash tools/r3/pmc_order.sh
 echo done

@@ -5,7 +5,7 @@ O=gpurun_out/r3batch
 mkdir -p $O
 for i in 1 2; do
 for b in 64 96 128 160; do
-timeout -k 10 300 python bench.py --batch $b --steps 3 --no-split --no-cpu-baseline --no-c4 > $O/c2_b$b.$i.json 2> $O/c2_b$b.$i.err
+timeout -k 10 300 python bench.py --full --batch $b --steps 3 --no-split --no-cpu-baseline --no-c4 > $O/c2_b$b.$i.json 2> $O/c2_b$b.$i.err
 done
 done
 for b in 64 96 128; do

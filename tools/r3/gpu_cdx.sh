@@ -11,7 +11,7 @@ for f in 1 0; do
 SUTA_CONV_DX_PLANES=$f timeout -k 10 300 python bench.py --only-c4 --steps 2 > $O/c4_cdx$f.$i.json 2> $O/c4_cdx$f.$i.err
 done
 done
-timeout -k 10 300 python bench.py --steps 3 --no-split --no-cpu-baseline --no-c4 > $O/c2.json 2> $O/c2.err
+timeout -k 10 300 python bench.py --full --steps 3 --no-split --no-cpu-baseline --no-c4 > $O/c2.json 2> $O/c2.err
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/kt -- python3 bench.py --only-c4 --steps 1 --no-timing > $O/kt.log 2>&1
 python3 tools/trace_summary.py $(find $R/kt -name "*kernel_trace.csv" | head -1) > $O/c4_trace_summary.txt
 rm -rf $R

@@ -12,6 +12,6 @@ done
 done
 SUTA_DY_PLANES=1 timeout -k 10 400 python bench.py --only-c4 --c4-batch 164 --steps 2 > $O/c4_b164.json 2> $O/c4_b164.err
 for b in 164 328; do
-timeout -k 10 400 python bench.py --batch $b --steps 3 --no-split --no-cpu-baseline --no-c4 > $O/c2_b$b.json 2> $O/c2_b$b.err
+timeout -k 10 400 python bench.py --full --batch $b --steps 3 --no-split --no-cpu-baseline --no-c4 > $O/c2_b$b.json 2> $O/c2_b$b.err
 done
 echo done

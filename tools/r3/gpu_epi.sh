@@ -7,7 +7,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 for i in 1 2; do
 for f in 1 0; do
 SUTA_EPI_FAST=$f timeout -k 10 300 python bench.py --only-c4 --steps 2 > $O/c4_fast$f.$i.json 2> $O/c4_fast$f.$i.err
-SUTA_EPI_FAST=$f timeout -k 10 300 python bench.py --steps 3 --no-split --no-cpu-baseline --no-c4 > $O/c2_fast$f.$i.json 2> $O/c2_fast$f.$i.err
+SUTA_EPI_FAST=$f timeout -k 10 300 python bench.py --full --steps 3 --no-split --no-cpu-baseline --no-c4 > $O/c2_fast$f.$i.json 2> $O/c2_fast$f.$i.err
 done
 done
 echo done

@@ -11,5 +11,5 @@ SUTA_HB_EPI_CLASS=$f timeout -k 10 300 python bench.py --only-c4 --steps 2 > $O/
 done
 done
 timeout -k 10 300 python tools/gemm_shapes.py > $O/c4_gemm_shapes.txt 2>&1
-timeout -k 10 300 python bench.py --steps 3 --no-split --no-cpu-baseline --no-c4 > $O/c2.json 2> $O/c2.err
+timeout -k 10 300 python bench.py --full --steps 3 --no-split --no-cpu-baseline --no-c4 > $O/c2.json 2> $O/c2.err
 echo done

@@ -10,5 +10,5 @@ for p in 1 0; do
 SUTA_FLASH_FWD_PLANE=$p timeout -k 10 300 python bench.py --only-c4 --steps 2 > $O/c4_plane$p.$i.json 2> $O/c4_plane$p.$i.err
 done
 done
-timeout -k 10 400 python bench.py --steps 4 --no-split --no-cpu-baseline --no-c4 > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python bench.py --full --steps 4 --no-split --no-cpu-baseline --no-c4 > $O/bench.json 2> $O/bench.err
 echo done

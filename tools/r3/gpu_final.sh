@@ -5,5 +5,5 @@ export TMPDIR=/tmp
 O=gpurun_out/r3final
 mkdir -p $O
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
-timeout -k 10 700 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 700 python bench.py --full > $O/bench.json 2> $O/bench.err
 echo done

@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r3ord
 R=/tmp/r3ord_raw
 mkdir -p $O $R
-B="python3 bench.py --steps 1 --warmup 0 --no-split --no-cpu-baseline --no-timing --no-c4"
+B="python3 bench.py --full --steps 1 --warmup 0 --no-split --no-cpu-baseline --no-timing --no-c4"
 csv() { find $R/$1 -name "*counter_collection.csv" | head -1; }
 for g in 8 4; do
 SUTA_GEMM_ORDER=$g timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $R/f$g -- $B > $O/f$g.log 2>&1

@@ -5,7 +5,7 @@ mkdir -p $O
 ( while sleep 50; do echo "tick $(date +%T)"; done ) &
 HB=$!
 trap "kill $HB" EXIT
-X="python bench.py --steps 2 --no-c4 --no-c5 --no-batch64 --no-split --no-cpu-baseline"
+X="python bench.py --full --steps 2 --no-c4 --no-c5 --no-batch64 --no-split --no-cpu-baseline"
 for i in 1 2; do
   for v in new alt; do
     if [ $v = alt ]; then export SUTA_LIB=$2; else unset SUTA_LIB; fi

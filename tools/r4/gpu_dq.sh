@@ -16,6 +16,6 @@ for i in 1 2; do
   done
 done
 for x in 1 0; do
-  SUTA_DQ_INLAUNCH=$x timeout -k 10 300 python bench.py --steps 2 --no-c4 --no-c5 --no-batch64 --no-split --no-cpu-baseline > $O/c2_dq$x.json 2> $O/c2_dq$x.err
+  SUTA_DQ_INLAUNCH=$x timeout -k 10 300 python bench.py --full --steps 2 --no-c4 --no-c5 --no-batch64 --no-split --no-cpu-baseline > $O/c2_dq$x.json 2> $O/c2_dq$x.err
   python -c "import json; d=json.loads(open('$O/c2_dq$x.json').read().strip().splitlines()[-1]); print('c2 dq=$x', d['value'], d['roofline']['frac'], d['attention'])"
 done

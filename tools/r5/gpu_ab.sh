@@ -18,7 +18,7 @@ run() {  # $1 variant, $2 round, $3 c2|c4
     env $envs timeout -k 10 300 python bench.py --only-c4 --steps 4 > $O/c4_$tag.$2.json 2> $O/c4_$tag.$2.err
     python -c "import json; d=json.load(open('$O/c4_$tag.$2.json')); print('C4 $1', d['value'], d['roofline']['frac'], 'attn', d['attention']['tflops'], d['time_breakdown_ms'])"
   else
-    env $envs timeout -k 10 300 python bench.py --no-c4 --no-c5 --no-batch64 --no-split --no-cpu-baseline --steps 4 > $O/c2_$tag.$2.json 2> $O/c2_$tag.$2.err
+    env $envs timeout -k 10 300 python bench.py --full --no-c4 --no-c5 --no-batch64 --no-split --no-cpu-baseline --steps 4 > $O/c2_$tag.$2.json 2> $O/c2_$tag.$2.err
     python -c "import json; d=json.load(open('$O/c2_$tag.$2.json')); print('C2 $1', d['value'], d['roofline']['frac'], 'attn', d['attention']['tflops'], d.get('time_breakdown_ms'))"
   fi
 }

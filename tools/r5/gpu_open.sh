@@ -6,7 +6,7 @@ mkdir -p $O
 ( while sleep 50; do echo "tick $(date +%T)"; done ) &
 HB=$!
 trap "kill $HB" EXIT
-timeout -k 10 700 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 700 python bench.py --full > $O/bench.json 2> $O/bench.err
 python - <<PY
 import json
 d = json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

@@ -9,7 +9,7 @@ trap "kill $HB" EXIT
 timeout -k 10 1000 python -u -m pytest tests -m gpu -x -v --timeout 500 --timeout-method thread > $O/gpu_tests.log 2>&1 || { tail -60 $O/gpu_tests.log; exit 1; }
 tail -2 $O/gpu_tests.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
-timeout -k 10 700 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 700 python bench.py --full > $O/bench.json 2> $O/bench.err
 python - <<PY
 import json
 d = json.loads(open("$O/bench.json").read().strip().splitlines()[-1])
