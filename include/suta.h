@@ -56,7 +56,7 @@ typedef struct suta_model_config {
     int32_t num_hidden_layers;             /* 12 / 24 */
     int32_t num_attention_heads;           /* 12 / 16 */
     int32_t intermediate_size;             /* 3072 / 4096 */
-    int32_t vocab_size;                    /* 32 */
+    int32_t vocab_size;                    /* 32; 1 .. 1024 */
     int32_t num_conv_layers;               /* 7 */
     int32_t conv_dim[SUTA_MAX_CONV];
     int32_t conv_kernel[SUTA_MAX_CONV];
@@ -103,7 +103,10 @@ typedef struct suta_hparams {
 /* Weights: `n` tensors named by their HF state_dict key (e.g.
  * "wav2vec2.encoder.layers.0.attention.q_proj.weight"), float32, host memory, HF layout.
  * max_samples: longest utterance any later call may pass (the reference truncates to 600000,
- * data.py); longer inputs return SUTA_ERR_ARG; <= 0 means no limit beyond T <= 2048 frames. */
+ * data.py); longer inputs return SUTA_ERR_ARG; <= 0 means no limit beyond T <= 2048 frames.
+ * cfg->vocab_size: 1 .. 1024 (any Wav2Vec2ForCTC head: letters, XLSR fine-tunes, phoneme sets); larger
+ * returns SUTA_ERR_UNSUPPORTED.  Class 0 is the CTC blank of the non-blank mask, as the reference
+ * hard-codes it (main.py:178-184).  The SDPL objective (pl_coef > 0) needs vocab_size <= 32. */
 int32_t suta_create(const suta_model_config* cfg, const char* const* names, const float* const* data,
                     const int64_t* numels, int32_t n, int32_t device, int32_t max_batch,
                     int64_t max_samples, suta_engine** out);
@@ -164,7 +167,12 @@ int32_t suta_adapt_varlen(suta_engine* e, const float* wav, int32_t wav_on_devic
 
 /* The fused entropy+MCC loss-and-gradient kernel alone (softmax_entropy / mcc_loss / div_loss and
  * the loss assembly of main.py:26-60, 181-203) on `batch` host logit blocks of T x vocab.
- * dlogits_out: batch x T x vocab (host); loss_out: batch floats (host). */
+ * dlogits_out: batch x T x vocab (host); loss_out: batch floats (host).
+ * Class-count rule: the MCC term is divided by 32 whatever vocab_size is, because the reference's
+ * mcc_loss is always called with its default class_num=32 (main.py:30, 42, 198).  vocab_size <= 64 runs
+ * the one-block-per-utterance kernel, 65 .. 1024 the any-vocabulary kernels (fp64 arithmetic; with
+ * SUTA_LOSS_WIDE=1 in the environment at every size).  The loss is fp32-or-better in every
+ * precision mode. */
 int32_t suta_loss_grad(suta_engine* e, const float* logits, int32_t batch, int64_t frames,
                        const suta_hparams* hp, float* dlogits_out, float* loss_out);
 

@@ -96,6 +96,8 @@ struct SutaSwitches {
                           // (tests); 0 = gemm_hbt_kernel (128 x 128, two stages, split-K on small grids)
     int epi_fast;         // SUTA_EPI_FAST (default 1): 32-bit-offset GEMM epilogue where every operand fits 4 GiB (p.off32);
                           // 0 = the general epilogue everywhere
+    int loss_wide;        // SUTA_LOSS_WIDE (default 0): 1 = the any-vocabulary loss path (ops.hip loss_wide_*) also at
+                          // vocab_size <= 64, where the one-block-per-utterance kernel runs by default (tests)
 };
 void suta_latch_switches();
 // hipFuncSetAttribute(fn, MaxDynamicSharedMemorySize, bytes) once per kernel, thread-safe (ops.hip)

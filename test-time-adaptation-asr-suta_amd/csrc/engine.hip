@@ -634,7 +634,7 @@ void suta_engine::build_plan(int B, long N) {
         pl.dpart = ar.take<double>((size_t)B * ((pl.Lc[0] + 127) / 128 + 2) * 2 * k.C[0] + (size_t)B * k.C[0] * 2);
         pl.c0part = ar.take<float>((size_t)B * ((pl.Lc[0] + 127) / 128) * k.K[0] * k.C[0] + 64);
         pl.loss = ar.take<float>(B);
-        pl.loss_scratch = ar.take<float>((size_t)B * T * 66 + 64);
+        pl.loss_scratch = ar.take<float>(suta_loss_scratch_floats(B, T, k.V));  // either loss path (ops.h)
         pl.ids = ar.take<int>((size_t)BT);
         pl.len_n = ar.take<int>((size_t)B);
         pl.len_L0 = ar.take<int>((size_t)B);
@@ -1936,7 +1936,9 @@ Cfg make_cfg(const suta_model_config* m) {
     c.eps = m->layer_norm_eps;
     if (c.H % c.NH || c.H % c.posG) throw SutaError(SUTA_ERR_ARG, "hidden_size not divisible by heads/groups");
     if ((c.H / c.posG) % 16) throw SutaError(SUTA_ERR_UNSUPPORTED, "pos-conv group width must be a multiple of 16");
-    if (c.V > 64) throw SutaError(SUTA_ERR_UNSUPPORTED, "vocab_size > 64");
+    if (c.V < 1) throw SutaError(SUTA_ERR_ARG, "vocab_size < 1");
+    if (c.V > SUTA_MAX_VOCAB)
+        throw SutaError(SUTA_ERR_UNSUPPORTED, "vocab_size > 1024 (the loss path handles 1 <= vocab_size <= 1024)");
     if (c.H > 1024 || c.C[c.nconv - 1] > 1024) throw SutaError(SUTA_ERR_UNSUPPORTED, "hidden > 1024");
     return c;
 }
@@ -2309,14 +2311,16 @@ int32_t suta_loss_grad(suta_engine* e, const float* logits, int32_t batch, int64
     return guard([&] {
         if (batch < 1 || frames < 1) throw SutaError(SUTA_ERR_ARG, "empty logits");
         HIPCHK(hipSetDevice(e->device));
+        suta_latch_switches();  // SUTA_LOSS_WIDE picks the loss path
         const int V = e->c.V;
         const size_t n = (size_t)batch * frames * V;
+        const size_t nscr = suta_loss_scratch_floats(batch, frames, V);
         DevBuf buf;
-        buf.alloc((2 * n + (size_t)batch * frames * 66 + 64 + batch) * sizeof(float));
-        float* dl = buf.p;
+        buf.alloc((nscr + 2 * n + batch) * sizeof(float));
+        float* scr = buf.p;  // first: the wide path reads it as doubles (8-byte aligned)
+        float* dl = scr + nscr;
         float* dd = dl + n;
-        float* scr = dd + n;
-        float* ls = scr + (size_t)batch * frames * 66 + 64;
+        float* ls = dd + n;
         HIPCHK(hipMemcpyAsync(dl, logits, n * 4, hipMemcpyHostToDevice, e->st));
         LossHP lh{hp->temp, hp->em_coef, hp->div_coef, hp->reweight, hp->non_blank};
         launch_suta_loss(dl, batch, (int)frames, V, lh, nullptr, dd, ls, scr, e->st);

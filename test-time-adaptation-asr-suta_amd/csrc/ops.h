@@ -102,6 +102,12 @@ struct LossHP {
 };
 // tlen (device, may be null): ragged batch, utterance b has tlen[b] <= T frames at stride T; the
 // gradient of its padding frames is written as 0.
+// V <= 64: one fused kernel, a block per utterance.  64 < V <= SUTA_MAX_VOCAB, or any V with the SUTA_LOSS_WIDE
+// switch: the matrix-free fp64 path (five kernels, a wave per frame / a block per 64-class chunk; ops.hip).  Both
+// divide the MCC term by the reference's class_num default 32, whatever V is.  scratch: 8-byte aligned,
+// suta_loss_scratch_floats(B, T, V) floats (enough for either path).
+#define SUTA_MAX_VOCAB 1024
+size_t suta_loss_scratch_floats(int B, long T, int V);
 void launch_suta_loss(const float* logits, int B, int T, int V, LossHP hp, const int* tlen, float* dlogits, float* loss,
                       float* scratch, hipStream_t st);
 
@@ -112,7 +118,7 @@ long sdpl_scratch_floats(int T);
 void launch_sdpl_loss(const float* logits, int B, int T, int V, float pl_coef, const int* tlen, float* dlogits,
                       float* loss, float* scratch, int* err, hipStream_t st);
 
-// Argmax ids per frame (first max, like torch.argmax), optional copy of logits.
+// Argmax ids per frame (first max, like torch.argmax): a row per thread for V <= 64, a wave per row above.
 void launch_argmax(const float* logits, long rows, int V, int* ids, hipStream_t st);
 
 // AdamW single-tensor semantics with per-run multiplicity k (k sub-steps with the same gradient).

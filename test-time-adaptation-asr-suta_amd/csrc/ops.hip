@@ -1156,8 +1156,12 @@ __global__ __launch_bounds__(256) void dgelu_mul_kernel(const float* __restrict_
 
 // ------------------------------------------------------------------------------------------
 // fused SUTA loss + gradient, one 256-thread block per utterance, V <= 64 (lane = class)
+// The MCC term divides by the reference's mcc_loss default class_num = 32 (main.py:30, 42; the call at
+// main.py:198 never passes the vocabulary size), not by V.
 // scratch per utterance: P[T][64], H[T] (floats)
 // ------------------------------------------------------------------------------------------
+constexpr int MCC_CLASS_NUM = 32;
+
 __global__ __launch_bounds__(256) void suta_loss_kernel(const float* __restrict__ logits, int T, int V, LossHP hp,
                                                         float* __restrict__ dlogits, float* __restrict__ loss_out,
                                                         float* __restrict__ scratch, const int* __restrict__ tlen) {
@@ -1272,12 +1276,12 @@ __global__ __launch_bounds__(256) void suta_loss_kernel(const float* __restrict_
             rvec[j] = s;
         }
         __syncthreads();
-        if (threadIdx.x < V) {  // rho_a = sum_i G_ia C_ia / r_a^2, G = (1 - delta)/V
+        if (threadIdx.x < V) {  // rho_a = sum_i G_ia C_ia / r_a^2, G = (1 - delta)/32
             const int a = threadIdx.x;
             double s = 0.0;
             for (int i = 0; i < V; ++i)
                 if (i != a) s += Cm[i * 64 + a];
-            rho[a] = s / V / (rvec[a] * rvec[a]);
+            rho[a] = s / MCC_CLASS_NUM / (rvec[a] * rvec[a]);
         }
         __syncthreads();
         double part = 0.0;
@@ -1286,12 +1290,12 @@ __global__ __launch_bounds__(256) void suta_loss_kernel(const float* __restrict_
             if (i != j) part += Cm[i * 64 + j] / rvec[j];
         }
         part = block_sum(part, &redd[0][0]);
-        mcc = part / V;
+        mcc = part / MCC_CLASS_NUM;
         // S = dC + dC^T, dC_ab = G_ab / r_b - rho_a
         for (int idx = threadIdx.x; idx < V * V; idx += 256) {
             const int a = idx / V, c = idx % V;
-            const double dab = (a != c ? 1.0 / V / rvec[c] : 0.0) - rho[a];
-            const double dba = (a != c ? 1.0 / V / rvec[a] : 0.0) - rho[c];
+            const double dab = (a != c ? 1.0 / MCC_CLASS_NUM / rvec[c] : 0.0) - rho[a];
+            const double dba = (a != c ? 1.0 / MCC_CLASS_NUM / rvec[a] : 0.0) - rho[c];
             Sm[a * 64 + c] = (float)(dab + dba);
         }
     }
@@ -1388,6 +1392,274 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ l
             bi = j;
         }
     ids[r] = bi;
+}
+
+// One wave per row (V > 64): each lane scans its classes in ascending order, then the (value, index) pairs are
+// reduced with the lower index winning a tie: the first maximum, as the row-per-thread form above.
+__device__ __forceinline__ int wave_argmax_row(const float* __restrict__ l, int V, int lane) {
+    float bv = -INFINITY;
+    int bi = 1 << 30;
+    if (lane < V) {
+        bv = l[lane];
+        bi = lane;
+    }
+    for (int c = lane + 64; c < V; c += 64)
+        if (l[c] > bv) {
+            bv = l[c];
+            bi = c;
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ov > bv || (ov == bv && oi < bi)) {
+            bv = ov;
+            bi = oi;
+        }
+    }
+    return bi;
+}
+
+__global__ __launch_bounds__(256) void argmax_wave_kernel(const float* __restrict__ logits, long rows, int V,
+                                                          int* __restrict__ ids) {
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const int bi = wave_argmax_row(logits + r * V, V, lane);
+    if (lane == 0) ids[r] = bi;
+}
+
+// ------------------------------------------------------------------------------------------
+// SUTA loss + gradient for any class count (1 <= V <= 1024): five small kernels, fp64 throughout.
+//
+// The MCC term never needs the V x V matrix C = P^T diag(w) P itself.  With softmax rows (sum_k p_tk = 1):
+//   r_a   = sum_k C_ak = sum_t w_t p_ta                      (torch.sum(C, dim=1); C is symmetric)
+//   o_a   = sum_{i != a} C_ia = sum_t w_t p_ta (1 - p_ta)    (column sum without the diagonal)
+//   mcc   = sum_a (o_a / r_a) / 32                           (mcc_loss's class_num default: 32 whatever V is)
+//   dmcc/dC_ab = (1 - delta_ab) / (32 r_b) - rho_a,  rho_a = o_a / (32 r_a^2)
+//   dP_tj = w_t sum_a p_ta (dC_aj + dC_ja) = w_t ((1 - 2 p_tj) / (32 r_j) - rho_j) + (a term constant in j)
+// and the softmax backward p_j (dP_j - sum_k p_k dP_k) drops what is constant in j.  So the loss and its gradient
+// are row reductions over V and column reductions over T, O(T V) work instead of two 2 V^2 T products.
+//
+// scratch (doubles): rows[B*Tl][5] = {max z, log sum exp, H, w_hat, non-blank}; utt[B][8] = {K, sum(1 + e^-H),
+// sum_m H, sum H, H_q}; cls[B][V][5] = {r | 1/(32 r), o | rho, sum_t logit | q, log q, -}.
+// Probabilities are recomputed from (max, lse) in each pass (same expression, same bits).  Every sum has a fixed
+// order: per-lane strided partials, the xor butterfly, then waves 0..3.
+// ------------------------------------------------------------------------------------------
+constexpr int LW_ROW = 5, LW_UTT = 8, LW_CLS = 5;
+
+__device__ __forceinline__ double block_max_d(double v, double* red) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    __syncthreads();
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    const double s = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+    __syncthreads();
+    return s;
+}
+
+// one wave per frame: softmax statistics at temperature, entropy, raw-logit argmax mask; padding frames' gradient = 0
+__global__ __launch_bounds__(256) void loss_wide_rows_kernel(const float* __restrict__ logits, int Tl, int V, long rows,
+                                                             double temp, float* __restrict__ dlogits,
+                                                             double* __restrict__ rowd, const int* __restrict__ tlen) {
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const int b = (int)(r / Tl), t = (int)(r % Tl);
+    const float* l = logits + r * V;
+    if (tlen && t >= tlen[b]) {
+        float* d = dlogits + r * V;
+        for (int c = lane; c < V; c += 64) d[c] = 0.f;
+        return;
+    }
+    const int bi = wave_argmax_row(l, V, lane);
+    double mx = -INFINITY;
+    for (int c = lane; c < V; c += 64) mx = fmax(mx, (double)l[c] / temp);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+    double s = 0.0, u = 0.0;  // sum e, sum e (z - max)
+    for (int c = lane; c < V; c += 64) {
+        const double zc = (double)l[c] / temp - mx;
+        const double e = exp(zc);
+        s += e;
+        u += e * zc;
+    }
+    s = wave_sum_d(s);
+    u = wave_sum_d(u);
+    if (lane == 0) {
+        const double lse = log(s);
+        double* o = rowd + r * LW_ROW;
+        o[0] = mx;
+        o[1] = lse;
+        o[2] = lse - u / s;  // H = -sum p log p, log p = z - max - lse
+        o[4] = bi != 0 ? 1.0 : 0.0;
+    }
+}
+
+// one block per utterance: K, the reweighting normaliser, the entropy sums; then w_hat per frame
+__global__ __launch_bounds__(256) void loss_wide_utt_kernel(int Tl, int reweight, double* __restrict__ rowd,
+                                                            double* __restrict__ utt, const int* __restrict__ tlen) {
+    __shared__ double red[4];
+    const int b = blockIdx.x;
+    const int T = tlen ? tlen[b] : Tl;
+    double* R = rowd + (long)b * Tl * LW_ROW;
+    double k = 0.0, ws = 0.0, hm = 0.0, ha = 0.0;
+    for (int t = threadIdx.x; t < T; t += 256) {
+        const double H = R[(long)t * LW_ROW + 2], m = R[(long)t * LW_ROW + 4];
+        k += m;
+        ws += 1.0 + exp(-H);
+        hm += m * H;
+        ha += H;
+    }
+    k = block_sum(k, red);
+    ws = block_sum(ws, red);
+    hm = block_sum(hm, red);
+    ha = block_sum(ha, red);
+    if (threadIdx.x == 0) {
+        double* u = utt + (long)b * LW_UTT;
+        u[0] = k;
+        u[1] = ws;
+        u[2] = hm;
+        u[3] = ha;
+    }
+    for (int t = threadIdx.x; t < T; t += 256)
+        R[(long)t * LW_ROW + 3] = reweight ? (double)T * (1.0 + exp(-R[(long)t * LW_ROW + 2])) / ws : 1.0;
+}
+
+// block (chunk of 64 classes, utterance): sums over the frames; wave w takes frames t = w (mod 4)
+__global__ __launch_bounds__(256) void loss_wide_cols_kernel(const float* __restrict__ logits, int Tl, int V,
+                                                             double temp, const double* __restrict__ rowd,
+                                                             double* __restrict__ cls, const int* __restrict__ tlen) {
+    __shared__ double part[4][3][64];
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lane;
+    const int T = tlen ? tlen[b] : Tl;
+    const float* L = logits + (long)b * Tl * V;
+    const double* R = rowd + (long)b * Tl * LW_ROW;
+    double r = 0.0, o = 0.0, cs = 0.0;
+    if (c < V)
+        for (int t = w; t < T; t += 4) {
+            const double l = L[(long)t * V + c];
+            const double* rt = R + (long)t * LW_ROW;
+            const double p = exp(l / temp - rt[0] - rt[1]);
+            const double wp = rt[3] * p;
+            r += wp;
+            o += wp * (1.0 - p);
+            cs += l;
+        }
+    part[w][0][lane] = r;
+    part[w][1][lane] = o;
+    part[w][2][lane] = cs;
+    __syncthreads();
+    if (w == 0 && c < V) {
+        double* out = cls + ((long)b * V + c) * LW_CLS;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) out[j] = ((part[0][j][lane] + part[1][j][lane]) + part[2][j][lane]) + part[3][j][lane];
+    }
+}
+
+// one block per utterance: the MCC value and its per-class gradient coefficients, the div-loss softmax, the loss
+__global__ __launch_bounds__(256) void loss_wide_finish_kernel(int Tl, int V, LossHP hp, double* __restrict__ cls,
+                                                               double* __restrict__ utt, float* __restrict__ loss_out,
+                                                               const int* __restrict__ tlen) {
+    __shared__ double red[4];
+    const int b = blockIdx.x;
+    const int T = tlen ? tlen[b] : Tl;
+    double* C = cls + (long)b * V * LW_CLS;
+    double* u = utt + (long)b * LW_UTT;
+    const double em = hp.em_coef, g = 1.0 / MCC_CLASS_NUM;
+    const bool use_mcc = 1.0f - hp.em_coef > 0.f;
+    double mcc = 0.0;
+    if (use_mcc) {
+        for (int c = threadIdx.x; c < V; c += 256) {
+            const double r = C[c * LW_CLS + 0], o = C[c * LW_CLS + 1];
+            mcc += o / r;
+            C[c * LW_CLS + 0] = g / r;
+            C[c * LW_CLS + 1] = g * o / (r * r);
+        }
+        mcc = block_sum(mcc, red) * g;
+    }
+    double Hq = 0.0;
+    if (hp.div_coef > 0.f) {  // q = softmax(mean_t logits[1:])
+        double mx = -INFINITY;
+        for (int c = 1 + threadIdx.x; c < V; c += 256) mx = fmax(mx, C[c * LW_CLS + 2] / T);
+        mx = block_max_d(mx, red);
+        double s = 0.0;
+        for (int c = 1 + threadIdx.x; c < V; c += 256) s += exp(C[c * LW_CLS + 2] / T - mx);
+        s = block_sum(s, red);
+        const double lse = log(s);
+        double h = 0.0;
+        for (int c = 1 + threadIdx.x; c < V; c += 256) {
+            const double lq = C[c * LW_CLS + 2] / T - mx - lse;
+            const double q = exp(lq);
+            C[c * LW_CLS + 2] = q;
+            C[c * LW_CLS + 3] = lq;
+            h -= q * lq;
+        }
+        Hq = block_sum(h, red);
+    }
+    if (threadIdx.x == 0) {
+        u[4] = Hq;
+        if (loss_out) {
+            double lv = 0.0;
+            if (hp.em_coef > 0.f) {
+                if (hp.non_blank) lv += em * (u[0] > 0 ? u[2] / u[0] : (double)NAN);
+                else lv += em * u[3] / T;
+            }
+            if (use_mcc) lv += (1.0 - em) * mcc;
+            if (hp.div_coef > 0.f) lv += (double)hp.div_coef * (-Hq);
+            loss_out[b] = (float)lv;
+        }
+    }
+}
+
+// one wave per frame: dL/dlogits
+__global__ __launch_bounds__(256) void loss_wide_grad_kernel(const float* __restrict__ logits, int Tl, int V, long rows,
+                                                             LossHP hp, const double* __restrict__ rowd,
+                                                             const double* __restrict__ utt,
+                                                             const double* __restrict__ cls, float* __restrict__ dlogits,
+                                                             const int* __restrict__ tlen) {
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const int b = (int)(r / Tl), t = (int)(r % Tl);
+    const int T = tlen ? tlen[b] : Tl;
+    if (t >= T) return;  // zeroed by the rows kernel
+    const float* l = logits + r * V;
+    float* d = dlogits + r * V;
+    const double* rt = rowd + r * LW_ROW;
+    const double* u = utt + (long)b * LW_UTT;
+    const double* C = cls + (long)b * V * LW_CLS;
+    const double temp = hp.temp, em = hp.em_coef;
+    const double mx = rt[0], lse = rt[1], H = rt[2], wt = rt[3];
+    const bool m = rt[4] != 0.0;
+    const bool use_mcc = 1.0f - hp.em_coef > 0.f;
+    double ce = 0.0;  // coefficient of dH_j = -p_j (log p_j + H)
+    if (hp.em_coef > 0.f) {
+        if (hp.non_blank) ce = (m && u[0] > 0) ? em / u[0] : 0.0;
+        else ce = em / T;
+    }
+    double sd = 0.0;  // sum_k p_k dP_k
+    if (use_mcc) {
+        for (int c = lane; c < V; c += 64) {
+            const double p = exp((double)l[c] / temp - mx - lse);
+            sd += p * (wt * (C[c * LW_CLS + 0] * (1.0 - 2.0 * p) - C[c * LW_CLS + 1]));
+        }
+        sd = wave_sum_d(sd);
+    }
+    const double dq = hp.div_coef > 0.f ? (double)hp.div_coef / T : 0.0, Hq = u[4];
+    for (int c = lane; c < V; c += 64) {
+        const double lp = (double)l[c] / temp - mx - lse;
+        const double p = exp(lp);
+        double dz = -ce * p * (lp + H);
+        if (use_mcc) dz += (1.0 - em) * p * (wt * (C[c * LW_CLS + 0] * (1.0 - 2.0 * p) - C[c * LW_CLS + 1]) - sd);
+        double gr = dz / temp;
+        if (dq > 0.0 && c >= 1) gr += dq * C[c * LW_CLS + 2] * (C[c * LW_CLS + 3] + Hq);
+        d[c] = (float)gr;
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1859,11 +2131,38 @@ void launch_dgelu_mul(const float* g, const float* z, float* out, long n, hipStr
 
 void launch_suta_loss(const float* logits, int B, int T, int V, LossHP hp, const int* tlen, float* dlogits, float* loss,
                       float* scratch, hipStream_t st) {
-    hipLaunchKernelGGL(suta_loss_kernel, dim3(B), dim3(256), 0, st, logits, T, V, hp, dlogits, loss, scratch, tlen);
+    if (V < 1 || V > SUTA_MAX_VOCAB) throw std::runtime_error("suta loss: vocab_size outside [1, 1024]");
+    if (V <= 64 && !suta_switches().loss_wide) {
+        hipLaunchKernelGGL(suta_loss_kernel, dim3(B), dim3(256), 0, st, logits, T, V, hp, dlogits, loss, scratch, tlen);
+        return;
+    }
+    // any V: rows -> utterance sums -> class sums -> utterance finish -> gradient rows (the layout above)
+    double* rowd = reinterpret_cast<double*>(scratch);
+    double* utt = rowd + (size_t)B * T * LW_ROW;
+    double* cls = utt + (size_t)B * LW_UTT;
+    const long rows = (long)B * T;
+    const dim3 rgrid((unsigned)((rows + 3) / 4));
+    const double temp = hp.temp;
+    hipLaunchKernelGGL(loss_wide_rows_kernel, rgrid, dim3(256), 0, st, logits, T, V, rows, temp, dlogits, rowd, tlen);
+    hipLaunchKernelGGL(loss_wide_utt_kernel, dim3(B), dim3(256), 0, st, T, hp.reweight, rowd, utt, tlen);
+    hipLaunchKernelGGL(loss_wide_cols_kernel, dim3((V + 63) / 64, B), dim3(256), 0, st, logits, T, V, temp, rowd, cls,
+                       tlen);
+    hipLaunchKernelGGL(loss_wide_finish_kernel, dim3(B), dim3(256), 0, st, T, V, hp, cls, utt, loss, tlen);
+    hipLaunchKernelGGL(loss_wide_grad_kernel, rgrid, dim3(256), 0, st, logits, T, V, rows, hp, rowd, utt, cls, dlogits,
+                       tlen);
+}
+
+size_t suta_loss_scratch_floats(int B, long T, int V) {
+    const size_t narrow = (size_t)B * T * 66 + 64;  // suta_loss_kernel: P[T][64], H[T], w[T] per utterance
+    const size_t wide = 2 * ((size_t)B * T * LW_ROW + (size_t)B * LW_UTT + (size_t)B * V * LW_CLS) + 64;  // doubles
+    return std::max(narrow, wide);
 }
 
 void launch_argmax(const float* logits, long rows, int V, int* ids, hipStream_t st) {
-    hipLaunchKernelGGL(argmax_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, logits, rows, V, ids);
+    if (V > 64)
+        hipLaunchKernelGGL(argmax_wave_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, logits, rows, V, ids);
+    else
+        hipLaunchKernelGGL(argmax_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, logits, rows, V, ids);
 }
 
 __global__ __launch_bounds__(256) void broadcast_kernel(f32x4* __restrict__ dst, const f32x4* __restrict__ src,
@@ -1949,6 +2248,8 @@ void suta_latch_switches() {
     s.flash_fwd_nw = (fnw && atoi(fnw) == 8) ? 8 : 4;
     s.epi_fast = on("SUTA_EPI_FAST");
     s.hbp_conv = on("SUTA_HBP_CONV");
+    const char* lw = std::getenv("SUTA_LOSS_WIDE");
+    s.loss_wide = (lw && atoi(lw) != 0) ? 1 : 0;
     s.latched = 1;
     g_switches = s;
 }

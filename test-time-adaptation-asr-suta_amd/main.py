@@ -148,7 +148,9 @@ def workspace_bytes_per_audio_s(cfg) -> float:
     """Upper estimate of the engine's device workspace per second of padded audio in a batch (DESIGN.md section 2:
     measured 0.36 GB per 8 s base utterance = 45 MB/s): 50 frames/s x 4 B x layers x 14 H saved per frame in the
     encoder, plus ~3 fp32 buffers of the conv stack's 512 channels over its ~6350 frames per second."""
-    return 50 * 4 * cfg["num_hidden_layers"] * 14 * cfg["hidden_size"] + 6350 * 512 * 4 * 3
+    V = cfg.get("vocab_size", 32)
+    head = 50 * 4 * (2 * V + 66)   # logits, dlogits and the loss scratch per frame (larger vocabularies count)
+    return 50 * 4 * cfg["num_hidden_layers"] * 14 * cfg["hidden_size"] + 6350 * 512 * 4 * 3 + head
 
 
 def engine_fixed_bytes(cfg, weights, max_batch: int, precision: str = "fp32") -> float:
@@ -259,6 +261,14 @@ def main(argv=None, sdpl: bool = False):
         say(line)
 
     cfg, weights = load_model(a.asr, a.synthetic_weights)
+    if os.path.isfile(os.path.join(a.asr, "vocab.json")):   # --asr <local dir>: its own vocabulary (presets: built in)
+        import functools
+        from .decode import blank_notice, load_vocab
+        vocab = load_vocab(a.asr)
+        batch_decode = functools.partial(batch_decode, vocab=vocab)
+        note = blank_notice(vocab)
+        if note and rank == 0:
+            print(note, file=sys.stderr)
     # collect_params (main.py:79-80 prints every module name; main_SDPL.py's copy does not), setup_optimizer
     # (main.py:19-20), then print(param_names) (main.py:314, main_SDPL.py:321)
     from .modules import collect_params
