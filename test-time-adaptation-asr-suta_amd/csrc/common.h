@@ -98,6 +98,9 @@ struct SutaSwitches {
                           // 0 = the general epilogue everywhere
     int loss_wide;        // SUTA_LOSS_WIDE (default 0): 1 = the any-vocabulary loss path (ops.hip loss_wide_*) also at
                           // vocab_size <= 64, where the one-block-per-utterance kernel runs by default (tests)
+    int f32p;             // SUTA_F32P (default 1): the exact-fp32 GEMMs on the four-phase 256 x 256 kernel's fp32 forms
+                          // (gemm.hip use_f32p) on grids of >= 256 tiles; 2 = every eligible GEMM on any grid (tests);
+                          // 0 = the 128 x 128 LDS-DMA kernel everywhere
 };
 void suta_latch_switches();
 // hipFuncSetAttribute(fn, MaxDynamicSharedMemorySize, bytes) once per kernel, thread-safe (ops.hip)

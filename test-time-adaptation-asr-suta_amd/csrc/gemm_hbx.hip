@@ -923,16 +923,30 @@ __device__ __forceinline__ int hbp_swz(int r) { return (r >> 1) & 7; }
 // past K read the zero page.  The quadrants, phases, waits and epilogue are form 4's.
 __device__ __forceinline__ int tn_swz(int r) { return 2 * ((r & 3) | (((r >> 3) & 1) << 2)); }
 
-template <bool CB, int EM, int FORM, bool CONV, int DBG, bool TN = false>
+// F32 (form 3 only; gemm_run_f32p): exact-fp32 operands p.A / p.B on v_mfma_f32_32x32x2_f32, bitwise gemm_glds_kernel<..., 32,
+// 2>'s results.  A K-tile is 32 floats, so a half-tile image is the same 128 rows x 128 B and the DMA pieces, swizzle,
+// phases, waits and barriers are the bf16 form's; addresses below are kept in 2-byte units (an fp32 leading dimension
+// counts twice).  A 16-B fragment read holds the 4 consecutive k of four MFMAs: lane half h reads chunk 4 h + kk, i.e.
+// k = 16 h + 4 kk + e, the glds kernel's order (q = kk, then e) within each 32-deep step.
+//   F32 = 1: A and B k-contiguous (forward linears; with CONV the conv stack's input gradients);
+//   F32 = 2: B row-contiguous, B(k, n) = B[k ldb + n] (the linears' input gradients, the Z-batched conv forward): the
+//            B half-tile image is [32 k][128 columns] fp32 (512-B rows, the same 16 pieces of 1 KB), fragments are four
+//            4-byte reads per kk as glds_frag<..., KC = false>; the columns of rows k >= 16 are stored rotated by 32
+//            (on the DMA source) so the two lane halves of a read (k and k + 16) land on different banks.
+template <bool CB, int EM, int FORM, bool CONV, int DBG, bool TN = false, int F32 = 0>
 __device__ __forceinline__ void hbp_tile(const GemmParams& p, const TileId tid, char* const lds) {
     static_assert(!TN || (FORM == 4 && !CONV), "TN: form 4, no conv-A rows");
+    static_assert(!F32 || (FORM == 3 && !TN && !CB && !(CONV && F32 == 2)), "F32: form 3, fp32 outputs");
     // batch z (Z-batched GEMMs, the conv stack's per-utterance forward): operand planes offset in bf16 elements, the
     // epilogue's operands through a rebased copy of the parameters (batch z of a Z = 1 view)
     const int z1 = tid.z / p.zdiv, z0 = tid.z % p.zdiv;
-    const __bf16* A = reinterpret_cast<const __bf16*>(p.Ab) + z1 * p.sA1 + z0 * p.sA0;
-    const __bf16* B = reinterpret_cast<const __bf16*>(p.Bb) + z1 * p.sB1 + z0 * p.sB0;
+    const __bf16* A = F32 ? reinterpret_cast<const __bf16*>(p.A + z1 * p.sA1 + z0 * p.sA0)
+                          : reinterpret_cast<const __bf16*>(p.Ab) + z1 * p.sA1 + z0 * p.sA0;
+    const __bf16* B = F32 ? reinterpret_cast<const __bf16*>(p.B + z1 * p.sB1 + z0 * p.sB0)
+                          : reinterpret_cast<const __bf16*>(p.Bb) + z1 * p.sB1 + z0 * p.sB0;
+    const long lda2 = F32 ? 2 * p.lda : p.ldab, ldb2 = F32 ? 2 * p.ldb : p.ldbb;  // leading dimensions in 2-byte units
     const int m0 = tid.y * 256, n0 = tid.x * 256;
-    const int nk = TN ? (p.K + 63) / 64 : p.K / 64;
+    const int nk = TN ? (p.K + 63) / 64 : F32 ? p.K / 32 : p.K / 64;
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wr = wid >> 2, wc = wid & 3;
@@ -955,7 +969,7 @@ __device__ __forceinline__ void hbp_tile(const GemmParams& p, const TileId tid, 
                 const int q = h == 3 ? 1 : h == 2 ? 1 : 0;
                 const int gc = isa ? m0 + 128 * (ch >> 3) + 64 * q + 8 * (ch & 7) : n0 + 64 * (ch >> 2) + 32 * q + 8 * (ch & 3);
                 const bool ok = gc < (isa ? p.M : p.N);
-                const long ld = isa ? p.ldab : p.ldbb;
+                const long ld = isa ? lda2 : ldb2;
                 krow[i] = kr;
                 src[h][i] = ok ? (isa ? A : B) + (long)kr * ld + gc : reinterpret_cast<const __bf16*>(g_zero16);
                 inc[h][i] = ok ? (int)(64 * ld) : 0;
@@ -965,20 +979,29 @@ __device__ __forceinline__ void hbp_tile(const GemmParams& p, const TileId tid, 
             const int c = (lane & 7) ^ hbp_swz(lr);
             const bool isa = h == 0 || h == 3;
             const int q = h == 3 ? 1 : h == 2 ? 1 : 0;  // qm for A halves, qn for B halves
+            if (F32 == 2 && !isa) {  // piece = 2 image rows of 512 B; lane j: k row 2 pc + j / 32, slot j % 32
+                const int kr = 2 * pc + (lane >> 5);
+                const int ic = 4 * ((lane & 31) ^ ((kr >> 4) << 3));  // image column of the 16-B chunk (4 columns)
+                const int gc = n0 + (ic >> 5) * 64 + q * 32 + (ic & 31);
+                const bool ok = gc < p.N;
+                src[h][i] = ok ? B + (long)kr * ldb2 + 2 * gc : reinterpret_cast<const __bf16*>(g_zero16);
+                inc[h][i] = ok ? (int)(32 * ldb2) : 0;
+                continue;
+            }
             const int grow = isa ? m0 + (lr >> 6) * 128 + q * 64 + (lr & 63) : n0 + (lr >> 5) * 64 + q * 32 + (lr & 31);
             if (CONV && isa) {  // linear address of row grow - pad (validity decided per issue)
                 arow[h == 3 ? 1 : 0][i] = grow - p.pad;
-                src[h][i] = A + (long)(grow - p.pad) * p.ldab + 8 * c;
+                src[h][i] = A + (long)(grow - p.pad) * lda2 + 8 * c;
                 inc[h][i] = 64;
                 continue;
             }
             const bool ok = grow < (isa ? p.M : p.N);
-            const long ld = isa ? p.ldab : p.ldbb;
+            const long ld = isa ? lda2 : ldb2;
             src[h][i] = ok ? (isa ? A : B) + (long)grow * ld + 8 * c : reinterpret_cast<const __bf16*>(g_zero16);
             inc[h][i] = ok ? 64 : 0;
         }
-    const int spt = CONV ? p.segK / 64 : 1;          // K-tiles per segment
-    const long bjump = CONV ? p.sBseg - p.segK : 0;  // B address step at a segment boundary (bf16 elements)
+    const int spt = CONV ? p.segK / (F32 ? 32 : 64) : 1;                // K-tiles per segment
+    const long bjump = CONV ? (p.sBseg - p.segK) * (F32 ? 2 : 1) : 0;  // B address step at a segment boundary (2-byte units)
     // LDS image of half h in buffer b (images in the order A0, A1, B0, B1)
     auto himg = [&](int b, int h) -> char* {
         const int slot = h == 0 ? 0 : h == 3 ? 1 : h == 1 ? 2 : 3;
@@ -1023,7 +1046,7 @@ __device__ __forceinline__ void hbp_tile(const GemmParams& p, const TileId tid, 
         }
     };
     auto frag = [&](const char* img, int lr, int kk) {
-        const int c = 2 * kk + (lane >> 5);
+        const int c = F32 ? 4 * (lane >> 5) + kk : 2 * kk + (lane >> 5);
         return *reinterpret_cast<const bf16x8*>(img + lr * 128 + ((c ^ hbp_swz(lr)) << 4));
     };
     constexpr bool M16 = FORM == 4;
@@ -1086,7 +1109,17 @@ __device__ __forceinline__ void hbp_tile(const GemmParams& p, const TileId tid, 
     };
     auto read_b = [&](int b, int qn, bf16x8 (&fb)[4]) {
         const char* img = lds + (b * 4 + 2 + qn) * P_HALF;
-        if constexpr (TN) {
+        if constexpr (F32 == 2) {
+            const int hh = lane >> 5, ic = (wc * 32 + (lane & 31)) ^ (hh << 5);
+            const float* im = reinterpret_cast<const float*>(img) + 16 * hh * 128 + ic;
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                f32x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = im[(4 * kk + e) * 128];
+                fb[kk] = __builtin_bit_cast(bf16x8, v);
+            }
+        } else if constexpr (TN) {
 #pragma unroll
             for (int bn = 0; bn < 2; ++bn)
 #pragma unroll
@@ -1102,7 +1135,17 @@ __device__ __forceinline__ void hbp_tile(const GemmParams& p, const TileId tid, 
         }
     };
     auto mfma_q = [&](int qm, int qn, const bf16x8 (&fb)[4]) {
-        if constexpr (M16) {
+        if constexpr (F32 != 0) {
+#pragma unroll
+            for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk) {
+                    const f32x4 a = __builtin_bit_cast(f32x4, fa[bi][kk]), b = __builtin_bit_cast(f32x4, fb[kk]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        acc[2 * qm + bi][qn] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[e], a[e], acc[2 * qm + bi][qn], 0, 0, 0);
+                }
+        } else if constexpr (M16) {
 #pragma unroll
             for (int bm = 0; bm < 4; ++bm)
 #pragma unroll
@@ -1317,10 +1360,10 @@ __device__ __forceinline__ void hbp_tile(const GemmParams& p, const TileId tid, 
     }
 }
 
-template <bool CB, int EM, int FORM, bool CONV = false, int DBG = 0, bool TN = false>
+template <bool CB, int EM, int FORM, bool CONV = false, int DBG = 0, bool TN = false, int F32 = 0>
 __global__ __launch_bounds__(512, 1) void gemm_hbp_kernel(GemmParams p) {
     __shared__ __attribute__((aligned(16))) float smem[8 * P_HALF / 4];
-    hbp_tile<CB, EM, FORM, CONV, DBG, TN>(p, xcd_tile(p.order), reinterpret_cast<char*>(smem));
+    hbp_tile<CB, EM, FORM, CONV, DBG, TN, F32>(p, xcd_tile(p.order), reinterpret_cast<char*>(smem));
 }
 
 template <int MS, int EM, int TR = 0>
@@ -1399,6 +1442,50 @@ void gemm_run_hbt4(const GemmParams& p, dim3 grid, hipStream_t st) {
     if (!hbt4_ok(p)) throw std::invalid_argument("hbt4: outside the TN form's conditions");
     hipLaunchKernelGGL((gemm_hbp_kernel<false, EPI_BIAS | EPI_RESID | EPI_ROWMASK, 4, false, 0, true>), grid, dim3(512),
                        0, st, p);
+}
+
+// The exact-fp32 GEMMs on the four-phase 256 x 256 kernel (gemm_hbp_kernel's F32 forms, form-3 schedule; gemm.hip
+// use_f32p): 0 = not eligible, 1 = A and B k-contiguous (NT; with conv-A rows and per-tap weight segments: CONV),
+// 2 = B row-contiguous (NN).  fp32 operands and outputs, 16-B aligned with leading dimensions and batch strides in
+// whole 16-B chunks, K a multiple of the 32-float K-tile with at least four of them, no split-K, one of the three
+// epilogue classes, 32-bit epilogue offsets (p.off32 set by the caller), the staged C^T epilogue's operand conditions.
+int f32p_form(const GemmParams& p) {
+    auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    const int e = p.epi;
+    if (p.mode != 0 || p.Ab || p.Bb || p.Cb || p.preb || p.ta || !p.A || !p.B || !p.C) return 0;
+    if (p.K % 32 || p.K < 128 || p.splits > 1 || !p.off32 || (e & (EPI_ACCUM | EPI_SMBWD | EPI_DELTA))) return 0;
+    if ((e & ~XEM_A) && (e & ~XEM_G) && (e & ~XEM_D)) return 0;
+    if (!a16(p.A) || !a16(p.B) || p.lda % 4 || p.ldb % 4 || ((p.sA0 | p.sA1 | p.sB0 | p.sB1) % 4)) return 0;
+    if (p.segK > 0) {  // conv-A rows are the segments; only with per-tap weight segments, k-contiguous
+        if (!p.segB || !p.tb || p.segK % 32 || p.lda != p.segK || p.pad < 0 || p.zdiv != 1 || p.sBseg % 4 || (e & ~XEM_A & ~XEM_D))
+            return 0;
+    } else if (p.segB) {
+        return 0;
+    }
+    GemmParams q = p;  // (hbx_t_ok asks the bf16 planes' 8-element batch strides of the operands: checked above)
+    q.sA0 = q.sA1 = q.sB0 = q.sB1 = 0;
+    if (!hbx_t_ok(q, true)) return 0;
+    return p.tb ? 1 : 2;
+}
+
+void gemm_run_f32p(const GemmParams& p, dim3 grid, hipStream_t st) {
+    const int form = f32p_form(p), e = p.epi;
+    if (!form) throw std::invalid_argument("f32p: outside the fp32 four-phase form's conditions");
+#define F32P(EM_, CONV_, F_) \
+    hipLaunchKernelGGL((gemm_hbp_kernel<false, EM_, 3, CONV_, 0, false, F_>), grid, dim3(512), 0, st, p)
+    if (p.segK > 0) {
+        if ((e & ~XEM_A) == 0) F32P(XEM_A, true, 1);
+        else F32P(XEM_D, true, 1);
+    } else if (form == 1) {
+        if ((e & ~XEM_A) == 0) F32P(XEM_A, false, 1);
+        else if ((e & ~XEM_G) == 0) F32P(XEM_G, false, 1);
+        else F32P(XEM_D, false, 1);
+    } else {
+        if ((e & ~XEM_A) == 0) F32P(XEM_A, false, 2);
+        else if ((e & ~XEM_G) == 0) F32P(XEM_G, false, 2);
+        else F32P(XEM_D, false, 2);
+    }
+#undef F32P
 }
 
 // variant 1: v_mfma_f32_32x32x16_bf16 with the shared epilogue (class-specialised kernels for the linears' epilogue

@@ -1805,3 +1805,7 @@ bool hbt4_ok(const GemmParams& p);  // the conv weight gradients on the four-pha
 bool hbx_t_ok(const GemmParams& p, bool check_off32);
 // conv-A GEMM (segK > 0) eligible for the four-phase 256 x 256 kernel's CONV form (gemm_hbx.hip; p.off32 set)
 bool hbp_conv_ok(const GemmParams& p);
+// exact-fp32 GEMM eligible for the four-phase 256 x 256 kernel's fp32 forms (gemm_hbx.hip; p.off32 set): 0 = no,
+// 1 = A and B k-contiguous (also conv-A rows with weight segments), 2 = B row-contiguous
+int f32p_form(const GemmParams& p);
+void gemm_run_f32p(const GemmParams& p, dim3 grid, hipStream_t st);

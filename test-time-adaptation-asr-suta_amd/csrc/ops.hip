@@ -2250,6 +2250,8 @@ void suta_latch_switches() {
     s.hbp_conv = on("SUTA_HBP_CONV");
     const char* lw = std::getenv("SUTA_LOSS_WIDE");
     s.loss_wide = (lw && atoi(lw) != 0) ? 1 : 0;
+    const char* f32p = std::getenv("SUTA_F32P");
+    s.f32p = f32p ? std::min(2, std::max(0, atoi(f32p))) : 1;
     s.latched = 1;
     g_switches = s;
 }

@@ -1,10 +1,14 @@
 // Standalone fp32-MFMA GEMM microbenchmark + correctness check for the SUTA shapes.
 // Build (after make in csrc): hipcc -O3 --offload-arch=gfx950 -I test-time-adaptation-asr-suta_amd/csrc -c tools/gemm_bench.hip -o gb.o
-//        && hipcc --offload-arch=gfx950 gb.o test-time-adaptation-asr-suta_amd/csrc/gemm*.o -o tools/gemm_bench
+//        && hipcc --offload-arch=gfx950 gb.o -o tools/gemm_bench -L test-time-adaptation-asr-suta_amd -lsuta
+//           -Wl,-rpath,'$ORIGIN/../test-time-adaptation-asr-suta_amd'
+// usage: gemm_bench [check [variant [shape [mode]]]]   the variant sweep of the 128 x 128 family at 64 utterances
+//        gemm_bench f32p [batch]                       the 256 x 256 fp32 kernel against glds: bitwise check + timing
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 #include "common.h"
 
@@ -55,7 +59,95 @@ __global__ __launch_bounds__(256) void mfma_peak(float* out, int iters, float se
 struct Shape { const char* name; int M, N, K, Z, zdiv; int ta, tb; long lda, ldb, ldc, sA0, sA1, sB0, sB1, sC0, sC1;
                long Asz, Bsz, Csz; int segK, pad, Mvalid; double flops_scale; };
 
+// `gemm_bench f32p [batch]`: the fp32 four-phase 256 x 256 kernel (SUTA_F32P=2: gemm_hbp_kernel's fp32 forms) against the
+// 128 x 128 LDS-DMA kernel (SUTA_F32P=0) per shape, split-K off: the two outputs must be memcmp-equal (the same MFMA
+// products in the same k order), and both are timed.  Shapes: wav2vec2-base's linears and second conv layer at `batch`
+// utterances (default 164, the bench batch) and edge shapes the models never produce (4, 5 and 7 K-tiles; 1, 255, 257
+// and 300 rows; 256, 264 and 520 columns), each as NT and NN.
+struct PShape { const char* name; int M, N, K, Z, tb; long lda, ldb, ldc, sA1, sB1, sC1; int segK, pad, Mvalid; long sBseg; };
+
+static int run_f32p(int Bu) {
+    const int T = 399, H = 768, F = 3072, L1 = 12799, L0 = 25599;
+    const int M = Bu * T;
+    std::vector<PShape> S = {
+        {"ffn2_fwd NT", M, H, F, 1, 1, F, F, H, 0, 0, 0, 0, 0, 0, 0},
+        {"ffn1_fwd NT", M, F, H, 1, 1, H, H, F, 0, 0, 0, 0, 0, 0, 0},
+        {"qkv_fwd NT", M, 3 * H, H, 1, 1, H, H, 3 * H, 0, 0, 0, 0, 0, 0, 0},
+        {"oproj_fwd NT", M, H, H, 1, 1, H, H, H, 0, 0, 0, 0, 0, 0, 0},
+        {"dh1 NN", M, H, F, 1, 0, F, H, H, 0, 0, 0, 0, 0, 0, 0},
+        {"du NN", M, F, H, 1, 0, H, F, F, 0, 0, 0, 0, 0, 0, 0},
+        {"dqkv->dx NN", M, H, 3 * H, 1, 0, 3 * H, H, H, 0, 0, 0, 0, 0, 0, 0},
+        {"dattn NN", M, H, H, 1, 0, H, H, H, 0, 0, 0, 0, 0, 0, 0},
+        {"conv1_fwd NN", L1, 512, 1536, Bu, 0, 1024, 512, 512, (long)L0 * 512, 1536L * 512, (long)L1 * 512, 0, 0, 0, 0},
+        // conv1's input gradient, output-row residue 0 (taps 0 and 2): conv-A rows, per-tap weight segments
+        {"conv1_dx seg", (L0 + 1) / 2, 512, 1024, Bu, 1, 512, 512, 1024, (long)L1 * 512, 1536L * 512, (long)L0 * 512, 512, 1, L1,
+         -2L * 512 * 512},
+    };
+    static const int eM[] = {1, 255, 257, 300}, eN[] = {256, 264, 520}, eK[] = {128, 160, 224};
+    static char names[72][32];
+    int ni = 0;
+    for (int tb = 1; tb >= 0; --tb)
+        for (int m : eM)
+            for (int n : eN)
+                for (int k : eK) {
+                    snprintf(names[ni], sizeof names[ni], "edge %s %dx%dx%d", tb ? "NT" : "NN", m, n, k);
+                    S.push_back({names[ni++], m, n, k, 1, tb, k, tb ? k : n, n, 0, 0, 0, 0, 0, 0, 0});
+                }
+    long maxA = 0, maxB = 0, maxC = 0;
+    auto asz = [](const PShape& s) { return s.Z > 1 ? s.Z * s.sA1 : (long)s.M * s.lda; };
+    auto bsz = [](const PShape& s) { return s.Z > 1 ? s.Z * s.sB1 : (long)(s.tb ? s.N : s.K) * s.ldb; };
+    auto csz = [](const PShape& s) { return s.Z > 1 ? s.Z * s.sC1 : (long)s.M * s.ldc; };
+    for (auto& s : S) { maxA = std::max(maxA, asz(s)); maxB = std::max(maxB, bsz(s)); maxC = std::max(maxC, csz(s)); }
+    float *A, *B, *C;
+    CK(hipMalloc(&A, maxA * 4 + 4096)); CK(hipMalloc(&B, maxB * 4 + 4096)); CK(hipMalloc(&C, maxC * 4));
+    hipLaunchKernelGGL(fill, dim3((maxA + 255) / 256), dim3(256), 0, 0, A, maxA, 1u);
+    hipLaunchKernelGGL(fill, dim3((maxB + 255) / 256), dim3(256), 0, 0, B, maxB, 2u);
+    hipStream_t st; CK(hipStreamCreate(&st));
+    hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    setenv("SUTA_SPLITK", "0", 1);
+    gemm_set_mode(0);
+    gemm_set_variant(-1, 3);
+    int bad = 0;
+    printf("%-24s %6s %5s %5s %4s | %10s %7s | %10s %7s | %s\n", "shape", "M", "N", "K", "Z", "glds ms", "TF", "f32p ms", "TF",
+           "bitwise");
+    for (auto& s : S) {
+        GemmParams p; gemm_init(p);
+        p.A = A; p.B = B; p.C = C; p.M = s.M; p.N = s.N; p.K = s.K; p.Z = s.Z; p.tb = s.tb;
+        p.lda = s.lda; p.ldb = s.ldb; p.ldc = s.ldc; p.sA1 = s.sA1; p.sB1 = s.sB1; p.sC1 = s.sC1;
+        p.segK = s.segK; p.pad = s.pad; p.Mvalid = s.Mvalid; p.segB = s.segK > 0; p.sBseg = s.sBseg;
+        if (s.segK > 0) p.B = B + 2L * 512 * 512;  // the last tap's weight slice; the segments step back from it
+        const long n = csz(s);
+        const double flops = 2.0 * s.M * s.N * (double)s.K * s.Z;
+        std::vector<float> out[2];
+        float ms[2];
+        for (int v = 0; v < 2; ++v) {
+            setenv("SUTA_F32P", v ? "2" : "0", 1);
+            suta_latch_switches();
+            CK(hipMemsetAsync(C, 0xff, n * 4, st));
+            gemm_launch(p, st, nullptr, 0);
+            out[v].resize(n);
+            CK(hipMemcpyAsync(out[v].data(), C, n * 4, hipMemcpyDeviceToHost, st));
+            CK(hipStreamSynchronize(st));
+            const int it = flops > 1e10 ? 10 : 3;
+            CK(hipEventRecord(e0, st));
+            for (int i = 0; i < it; ++i) gemm_launch(p, st, nullptr, 0);
+            CK(hipEventRecord(e1, st));
+            CK(hipEventSynchronize(e1));
+            CK(hipEventElapsedTime(&ms[v], e0, e1));
+            ms[v] /= it;
+        }
+        const bool same = memcmp(out[0].data(), out[1].data(), n * 4) == 0;
+        bad += !same;
+        printf("%-24s %6d %5d %5d %4d | %10.3f %7.1f | %10.3f %7.1f | %s\n", s.name, s.M, s.N, s.K, s.Z, ms[0],
+               flops / (ms[0] * 1e-3) / 1e12, ms[1], flops / (ms[1] * 1e-3) / 1e12, same ? "equal" : "DIFFERENT");
+        fflush(stdout);
+    }
+    printf("%d shape(s) differ\n", bad);
+    return bad ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 2 && !strcmp(argv[1], "f32p")) return run_f32p(argc >= 3 ? atoi(argv[2]) : 164);
     const int Bu = 64, T = 399, Tp = 400, H = 768, F = 3072, L1 = 12799, L0 = 25599, NH = 12;
     std::vector<Shape> S = {
         {"ffn1_fwd NT", Bu*T, F, H, 1, 1, 0, 1, H, H, F, 0,0,0,0,0,0, (long)Bu*T*H, (long)F*H, (long)Bu*T*F, 0,0,0, 1},
