@@ -19,6 +19,8 @@
  *   suta_adapt_varlen    the same over utterances of different lengths in one batch
  *   suta_loss_grad       softmax_entropy + mcc_loss (+ div_loss) and loss.backward() w.r.t. the
  *                        logits (main.py:26-60, 181-205): the fused loss kernel alone
+ *   suta_set_pseudo_labels  the `vocab` dict and `processor` that main_SDPL.py hands to pseudo_labeling_loss
+ *                        (main_SDPL.py:194-203, 269-271): how each class id enters the pseudo-label target
  *   suta_get_param       model.state_dict()[name] of an adapted slot (main.py:139)
  *   suta_param_info      collect_params' entry multiplicity per trainable tensor
  *                        (main.py:79-94; duplicates => k Adam sub-steps per step)
@@ -106,7 +108,10 @@ typedef struct suta_hparams {
  * data.py); longer inputs return SUTA_ERR_ARG; <= 0 means no limit beyond T <= 2048 frames.
  * cfg->vocab_size: 1 .. 1024 (any Wav2Vec2ForCTC head: letters, XLSR fine-tunes, phoneme sets); larger
  * returns SUTA_ERR_UNSUPPORTED.  Class 0 is the CTC blank of the non-blank mask, as the reference
- * hard-codes it (main.py:178-184).  The SDPL objective (pl_coef > 0) needs vocab_size <= 32. */
+ * hard-codes it (main.py:178-184).  The SDPL objective (pl_coef > 0) runs at every vocab_size once
+ * suta_set_pseudo_labels has given it the checkpoint's own vocabulary; without a table it builds its pseudo labels
+ * by the 32-letter rule of facebook/wav2vec2-base-960h, which names a vocabulary only up to 32 classes: above that
+ * a call with pl_coef > 0 returns SUTA_ERR_UNSUPPORTED until a table is set. */
 int32_t suta_create(const suta_model_config* cfg, const char* const* names, const float* const* data,
                     const int64_t* numels, int32_t n, int32_t device, int32_t max_batch,
                     int64_t max_samples, suta_engine** out);
@@ -172,9 +177,33 @@ int32_t suta_adapt_varlen(suta_engine* e, const float* wav, int32_t wav_on_devic
  * mcc_loss is always called with its default class_num=32 (main.py:30, 42, 198).  vocab_size <= 64 runs
  * the one-block-per-utterance kernel, 65 .. 1024 the any-vocabulary kernels (fp64 arithmetic; with
  * SUTA_LOSS_WIDE=1 in the environment at every size).  The loss is fp32-or-better in every
- * precision mode. */
+ * precision mode.  With hp->pl_coef > 0 the SDPL kernels mix the pseudo-label CTC term in, as in suta_adapt.
+ * While timing is on, both launches count into family 4 (loss). */
 int32_t suta_loss_grad(suta_engine* e, const float* logits, int32_t batch, int64_t frames,
                        const suta_hparams* hp, float* dlogits_out, float* loss_out);
+
+/* The SDPL pseudo-label table (main_SDPL.py:194-203): the reference decodes the greedy ids with
+ * processor.batch_decode (group repeats, drop the pad token, the word delimiter becomes ' ', strip) and maps every
+ * character of that string through vocab.json, a space as '|'.  Per class id i of the engine's vocab_size V:
+ *   kinds[i] = SUTA_PL_NORMAL  the ids of the token's characters: ids[offsets[i] .. offsets[i + 1])
+ *              SUTA_PL_DROP    nothing (the pad token)
+ *              SUTA_PL_SPACE   a space (the word delimiter): dropped at both ends of the utterance, space_id inside,
+ *                              and a lookup failure inside when space_id is -1 (vocab.json has no '|')
+ *              SUTA_PL_FAIL    a character of the token is no token: the reference raises KeyError, the call that
+ *                              meets the id on the greedy path returns SUTA_ERR_UNSUPPORTED ("special token")
+ * offsets: V + 1 monotone entries from 0; every id in [1, V) (0 is the CTC blank).  Malformed input returns
+ * SUTA_ERR_ARG and leaves the table as it was.  All three pointers null takes the table away again: an
+ * engine of vocab_size <= 32 then follows the 32-letter rule of facebook/wav2vec2-base-960h (id 0 pad, 1..3 lookup
+ * failures, 4 the delimiter with space_id 4, every other id itself), a larger one refuses SDPL as before any table.  The table is part of suta_adapt's graph key.  A multi-character token can make the target
+ * longer than the frames allow (U + adjacent repeats > T); torch's CTCLoss then returns inf and NaN gradients,
+ * which the reference steps into its parameters.  The engine instead runs that step on an empty target and the
+ * call returns SUTA_ERR_UNSUPPORTED ("pseudo label longer than the utterance allows"). */
+#define SUTA_PL_NORMAL 0
+#define SUTA_PL_DROP 1
+#define SUTA_PL_SPACE 2
+#define SUTA_PL_FAIL 3
+int32_t suta_set_pseudo_labels(suta_engine* e, const int32_t* offsets, const int32_t* ids, const int32_t* kinds,
+                               int32_t space_id);
 
 /* Copy slot `slot`'s current value of trainable tensor `name` (HF layout) to host `out`. */
 int32_t suta_get_param(suta_engine* e, int32_t slot, const char* name, float* out, int64_t numel);

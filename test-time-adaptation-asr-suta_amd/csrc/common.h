@@ -101,6 +101,9 @@ struct SutaSwitches {
     int f32p;             // SUTA_F32P (default 1): the exact-fp32 GEMMs on the four-phase 256 x 256 kernel's fp32 forms
                           // (gemm.hip use_f32p) on grids of >= 256 tiles; 2 = every eligible GEMM on any grid (tests);
                           // 0 = the 128 x 128 LDS-DMA kernel everywhere
+    int sdpl_wide;        // SUTA_SDPL_WIDE (default 0): 1 = the any-vocabulary SDPL kernels (sdpl.hip sdpl_wide_*) also at
+                          // vocab_size <= 32 under the 960h pseudo-label rule, where the 32-letter kernels run by
+                          // default (tests, A/B timing)
 };
 void suta_latch_switches();
 // hipFuncSetAttribute(fn, MaxDynamicSharedMemorySize, bytes) once per kernel, thread-safe (ops.hip)

@@ -228,17 +228,44 @@ struct suta_engine {
     DevBuf sdpl_ws;  // SDPL CTC scratch (+ error flag), allocated on first use
     bool sdpl_used = false;
     int* sdpl_err = nullptr;
-    // after a call that ran the SDPL objective: a pseudo-label transcript held <s>, </s> or <unk>
+    // pseudo-label table (suta_set_pseudo_labels; the 960h rule until one is set): [off V+1 | kind V | ids] on the
+    // device.  Replacing it drops the captured loop, and pl_epoch is part of the graph key: a capture made with
+    // another table is never replayed.
+    int* pl_buf = nullptr;
+    SdplTable pl_tab{};
+    bool pl_default = true;  // the table is the 960h rule: V <= 32 runs the 32-letter kernels
+    bool pl_given = false;   // a caller's table is in place (suta_set_pseudo_labels), not the built-in rule
+    int pl_epoch = 0;
+    void set_pl_table(const std::vector<int>& off, const std::vector<int>& ids, const std::vector<int>& kind,
+                      int space_id);
+    void default_pl_table(std::vector<int>& off, std::vector<int>& ids, std::vector<int>& kind, int& space_id) const;
+    // null = the 32-letter kernels
+    // Above 32 classes the 32-letter rule names no vocabulary (which token is id 33?): SDPL there stays refused,
+    // as it always was, until the caller hands over the checkpoint's own table.
+    const SdplTable* sdpl_table() const {
+        if (c.V > 32 && !pl_given)
+            throw SutaError(SUTA_ERR_UNSUPPORTED,
+                            "SDPL objective at vocab_size > 32 needs the checkpoint's pseudo-label table "
+                            "(suta_set_pseudo_labels); without one only vocab_size <= 32 runs, by the 32-letter rule");
+        return (c.V <= 32 && pl_default && !suta_switches().sdpl_wide) ? nullptr : &pl_tab;
+    }
+    // after a call that ran the SDPL objective: the flags its kernels raised (ops.h SDPL_FLAG_*)
     void check_sdpl() {
         if (!sdpl_used) return;
         int e = 0;
         HIPCHK(hipMemcpy(&e, sdpl_err, sizeof(int), hipMemcpyDeviceToHost));
         HIPCHK(hipMemset(sdpl_err, 0, sizeof(int)));
         sdpl_used = false;
-        if (e)
+        if (e & SDPL_FLAG_LOOKUP)
             throw SutaError(SUTA_ERR_UNSUPPORTED,
-                            "SDPL pseudo label contains a special token (<s>, </s>, <unk>): the reference's "
-                            "vocab lookup raises KeyError (main_SDPL.py:196-200)");
+                            "SDPL pseudo label contains a special token (<s>, </s>, <unk>) or another character "
+                            "that is no token of the vocabulary: the reference's vocab lookup raises KeyError "
+                            "(main_SDPL.py:196-202)");
+        if (e & SDPL_FLAG_INFEASIBLE)
+            throw SutaError(SUTA_ERR_UNSUPPORTED,
+                            "SDPL pseudo label longer than the utterance allows: the expanded target has no CTC "
+                            "alignment in the utterance's frames (torch returns an inf loss and NaN gradients, "
+                            "main_SDPL.py:204-207); the step ran on an empty target, reset the engine");
     }
     // timing
     bool timing = false;
@@ -271,6 +298,7 @@ struct suta_engine {
         suta_hparams hp{};
         std::vector<int> rec;
         SutaSwitches sw{};  // the call's A/B switch snapshot (buffer formats and kernel choices captured)
+        int pl_epoch = 0;   // which pseudo-label table the SDPL kernels were captured with
     };
     hipGraphExec_t loop_graph = nullptr;
     int last_loop_mode = SUTA_LOOP_EAGER;  // suta_get_graph_stats
@@ -519,6 +547,7 @@ struct suta_engine {
 suta_engine::~suta_engine() {
     if (loop_graph) (void)hipGraphExecDestroy(loop_graph);
     if (d_adam_tab) (void)hipFree(d_adam_tab);
+    if (pl_buf) (void)hipFree(pl_buf);
     for (float* p : owned) (void)hipFree(p);
     for (auto& pe : pending) {
         (void)hipEventDestroy(pe.second.first);
@@ -1089,14 +1118,15 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
     timed(F_LOSS,
           [&] { launch_suta_loss(pl.logits, B, T, k.V, lh, rT(), pl.dlogits, pl.loss, pl.loss_scratch, st); });
     if (hp.pl_coef > 0.f) {  // SDPL: (1 - pl) * SUTA + pl * pseudo-label CTC (main_SDPL.py:143-209)
-        if (k.V > 32) throw SutaError(SUTA_ERR_UNSUPPORTED, "SDPL objective needs vocab_size <= 32");
-        const long per = sdpl_scratch_floats(T);
+        const long per = sdpl_scratch_floats(T, k.V);
         // [error flag | 63 pad | B x per-utterance scratch]: the flag stays at a fixed offset
         if (sdpl_ws.alloc(((size_t)B * per + 64) * sizeof(float)))
             HIPCHK(hipMemsetAsync(sdpl_ws.p, 0, sdpl_ws.bytes, st));
         int* err = reinterpret_cast<int*>(sdpl_ws.p);
+        const SdplTable* tab = sdpl_table();
         timed(F_LOSS, [&] {
-            launch_sdpl_loss(pl.logits, B, T, k.V, hp.pl_coef, rT(), pl.dlogits, pl.loss, sdpl_ws.p + 64, err, st);
+            launch_sdpl_loss(pl.logits, B, T, k.V, hp.pl_coef, rT(), pl.dlogits, pl.loss, sdpl_ws.p + 64, err,
+                             tab, st);
         });
         sdpl_used = true;
         sdpl_err = err;
@@ -1821,10 +1851,53 @@ void suta_engine::run_adapt_loop(int B, const suta_hparams& hp, int steps, const
 }
 
 // Key of this call; true when it equals the previous call's (graph capture pays off from the 2nd call)
+// The 960h rule at this engine's class count: id 0 pad, 1..3 lookup failures, 4 the delimiter (an inner space is
+// id 4 again), every other id itself (main_SDPL.py:194-203 with the vocab.json the reference ships).
+void suta_engine::default_pl_table(std::vector<int>& off, std::vector<int>& ids, std::vector<int>& kind,
+                                   int& space_id) const {
+    const int V = c.V;
+    off.assign(1, 0);
+    ids.clear();
+    kind.assign(V, SDPL_KIND_NORMAL);
+    for (int i = 0; i < V; ++i) {
+        if (i == 0) kind[i] = SDPL_KIND_DROP;
+        else if (i <= 3) kind[i] = SDPL_KIND_FAIL;
+        else if (i == 4) kind[i] = SDPL_KIND_SPACE;
+        else ids.push_back(i);
+        off.push_back((int)ids.size());
+    }
+    space_id = V > 4 ? 4 : -1;
+}
+
+void suta_engine::set_pl_table(const std::vector<int>& off, const std::vector<int>& ids, const std::vector<int>& kind,
+                               int space_id) {
+    const int V = c.V;
+    std::vector<int> h(off);
+    h.insert(h.end(), kind.begin(), kind.end());
+    h.insert(h.end(), ids.begin(), ids.end());
+    int* d = nullptr;
+    HIPCHK(hipSetDevice(device));
+    if (st) HIPCHK(hipStreamSynchronize(st));
+    drop_graph();
+    HIPCHK(hipMalloc(&d, h.size() * sizeof(int)));
+    if (pl_buf) (void)hipFree(pl_buf);
+    pl_buf = d;
+    HIPCHK(hipMemcpy(d, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
+    pl_tab.off = d;
+    pl_tab.kind = d + V + 1;
+    pl_tab.ids = d + 2 * V + 1;
+    pl_tab.space_id = space_id;
+    std::vector<int> doff, dids, dkind;
+    int dsp;
+    default_pl_table(doff, dids, dkind, dsp);
+    pl_default = off == doff && ids == dids && kind == dkind && space_id == dsp;
+    ++pl_epoch;
+}
+
 bool suta_engine::graph_key_repeats(const GraphKey& k) {
     const bool same = gkey_seen && gkey.B == k.B && gkey.N == k.N && gkey.ragged == k.ragged &&
                       gkey.mode == k.mode && gkey.steps == k.steps && gkey.want_logits == k.want_logits &&
-                      gkey.want_ids == k.want_ids && gkey.rec == k.rec &&
+                      gkey.want_ids == k.want_ids && gkey.rec == k.rec && gkey.pl_epoch == k.pl_epoch &&
                       std::memcmp(&gkey.hp, &k.hp, sizeof(suta_hparams)) == 0 &&
                       std::memcmp(&gkey.sw, &k.sw, sizeof(SutaSwitches)) == 0;
     if (!same) {
@@ -2141,6 +2214,13 @@ int32_t suta_create(const suta_model_config* cfg, const char* const* names, cons
             }
             e->bpos = up(b + "bias", H);
         }
+        {
+            std::vector<int> off, ids, kind;
+            int space_id;
+            e->default_pl_table(off, ids, kind, space_id);
+            e->set_pl_table(off, ids, kind, space_id);
+            e->pl_epoch = 0;
+        }
         e->reset_slots(max_batch, true);
         HIPCHK(hipStreamSynchronize(e->st));
         *out = e.release();
@@ -2195,6 +2275,7 @@ int32_t suta_step_ex(suta_engine* e, const float* wav, int32_t on_dev, int32_t n
         if (!logits_out) throw SutaError(SUTA_ERR_ARG, "logits_out is null");
         HIPCHK(hipSetDevice(e->device));
         suta_latch_switches();
+        if (hp->pl_coef > 0.f) (void)e->sdpl_table();  // refuses before any launch
         e->build_plan(batch, n);
         e->set_lengths(batch, nullptr);
         e->stage_input(wav, on_dev, norm, batch, n);
@@ -2233,6 +2314,7 @@ static void adapt_impl(suta_engine* e, const float* wav, int32_t on_dev, int32_t
     check_batch(e, batch, n);
     if (steps < 0) throw SutaError(SUTA_ERR_ARG, "steps < 0");
     suta_latch_switches();
+    if (hp->pl_coef > 0.f && steps > 0) (void)e->sdpl_table();  // refuses before any launch
     for (int i = 0; i < nrec; ++i)
         if (rec[i] < 0 || rec[i] > steps) throw SutaError(SUTA_ERR_ARG, "record step outside [0, steps]");
     HIPCHK(hipSetDevice(e->device));
@@ -2263,6 +2345,7 @@ static void adapt_impl(suta_engine* e, const float* wav, int32_t on_dev, int32_t
     key.hp = *hp;
     key.rec.assign(rec, rec + nrec);
     key.sw = suta_switches();
+    key.pl_epoch = e->pl_epoch;
     const bool graph_ok = e->graph_key_repeats(key);
     e->run_adapt_loop(batch, *hp, steps, rec, nrec, rec_logits, rec_ids, graph_ok);
     // the loop ran to completion with this key, so every buffer it needs is allocated now: a lazy allocation during
@@ -2313,6 +2396,7 @@ int32_t suta_loss_grad(suta_engine* e, const float* logits, int32_t batch, int64
         HIPCHK(hipSetDevice(e->device));
         suta_latch_switches();  // SUTA_LOSS_WIDE picks the loss path
         const int V = e->c.V;
+        const SdplTable* tab = hp->pl_coef > 0.f ? e->sdpl_table() : nullptr;  // refuses before any launch
         const size_t n = (size_t)batch * frames * V;
         const size_t nscr = suta_loss_scratch_floats(batch, frames, V);
         DevBuf buf;
@@ -2323,22 +2407,25 @@ int32_t suta_loss_grad(suta_engine* e, const float* logits, int32_t batch, int64
         float* ls = dd + n;
         HIPCHK(hipMemcpyAsync(dl, logits, n * 4, hipMemcpyHostToDevice, e->st));
         LossHP lh{hp->temp, hp->em_coef, hp->div_coef, hp->reweight, hp->non_blank};
-        launch_suta_loss(dl, batch, (int)frames, V, lh, nullptr, dd, ls, scr, e->st);
+        e->timed(F_LOSS, [&] { launch_suta_loss(dl, batch, (int)frames, V, lh, nullptr, dd, ls, scr, e->st); });
         DevBuf sbuf;
         if (hp->pl_coef > 0.f) {
-            if (V > 32) throw SutaError(SUTA_ERR_UNSUPPORTED, "SDPL objective needs vocab_size <= 32");
             if (frames > 2048) throw SutaError(SUTA_ERR_UNSUPPORTED, "T > 2048 frames");
-            const long per = sdpl_scratch_floats((int)frames);
+            const long per = sdpl_scratch_floats((int)frames, V);
             sbuf.alloc(((size_t)batch * per + 64) * sizeof(float));
             HIPCHK(hipMemsetAsync(sbuf.p, 0, sbuf.bytes, e->st));
             int* err = reinterpret_cast<int*>(sbuf.p);
-            launch_sdpl_loss(dl, batch, (int)frames, V, hp->pl_coef, nullptr, dd, ls, sbuf.p + 64, err, e->st);
+            e->timed(F_LOSS, [&] {
+                launch_sdpl_loss(dl, batch, (int)frames, V, hp->pl_coef, nullptr, dd, ls, sbuf.p + 64, err, tab,
+                                 e->st);
+            });
             e->sdpl_used = true;
             e->sdpl_err = err;
         }
         HIPCHK(hipMemcpyAsync(dlogits_out, dd, n * 4, hipMemcpyDeviceToHost, e->st));
         HIPCHK(hipMemcpyAsync(loss_out, ls, (size_t)batch * 4, hipMemcpyDeviceToHost, e->st));
         HIPCHK(hipStreamSynchronize(e->st));
+        if (e->timing) e->collect_timing();  // before the scratch buffers above go
         e->check_sdpl();
     });
 }
@@ -2427,6 +2514,40 @@ int32_t suta_set_precision(suta_engine* e, int32_t mode) {
         HIPCHK(hipSetDevice(e->device));
         if (mode == SUTA_PRECISION_BF16 && e->bf16_planes) e->build_weight_planes();
         e->gemm_mode = mode;
+    });
+}
+
+int32_t suta_set_pseudo_labels(suta_engine* e, const int32_t* offsets, const int32_t* ids, const int32_t* kinds,
+                               int32_t space_id) {
+    return guard([&] {
+        const int V = e->c.V;
+        if (!offsets && !ids && !kinds) {  // back to the 960h rule
+            std::vector<int> off, id, kind;
+            int sp;
+            e->default_pl_table(off, id, kind, sp);
+            e->set_pl_table(off, id, kind, sp);
+            e->pl_given = false;
+            return;
+        }
+        if (!offsets || !kinds) throw SutaError(SUTA_ERR_ARG, "pseudo-label table: offsets or kinds is null");
+        if (offsets[0] != 0) throw SutaError(SUTA_ERR_ARG, "pseudo-label table: offsets[0] != 0");
+        for (int i = 0; i < V; ++i) {
+            if (offsets[i + 1] < offsets[i]) throw SutaError(SUTA_ERR_ARG, "pseudo-label table: offsets not monotone");
+            if (kinds[i] < SDPL_KIND_NORMAL || kinds[i] > SDPL_KIND_FAIL)
+                throw SutaError(SUTA_ERR_ARG, "pseudo-label table: kind out of range");
+            if (kinds[i] != SDPL_KIND_NORMAL && offsets[i + 1] != offsets[i])
+                throw SutaError(SUTA_ERR_ARG, "pseudo-label table: only a normal token has an expansion");
+        }
+        const int n = offsets[V];
+        if (n > 0 && !ids) throw SutaError(SUTA_ERR_ARG, "pseudo-label table: ids is null");
+        for (int q = 0; q < n; ++q)
+            if (ids[q] <= 0 || ids[q] >= V)
+                throw SutaError(SUTA_ERR_ARG, "pseudo-label table: expansion id outside [1, vocab_size)");
+        if (space_id < -1 || space_id == 0 || space_id >= V)
+            throw SutaError(SUTA_ERR_ARG, "pseudo-label table: space_id outside {-1} and [1, vocab_size)");
+        e->set_pl_table(std::vector<int>(offsets, offsets + V + 1), std::vector<int>(ids, ids + n),
+                        std::vector<int>(kinds, kinds + V), space_id);
+        e->pl_given = true;
     });
 }
 

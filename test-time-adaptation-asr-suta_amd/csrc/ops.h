@@ -112,11 +112,26 @@ void launch_suta_loss(const float* logits, int B, int T, int V, LossHP hp, const
                       float* scratch, hipStream_t st);
 
 // SDPL pseudo-label CTC objective (main_SDPL.py:143-209; sdpl.hip): mixes pl_coef * L_ctc into the
-// SUTA loss / gradient already in loss / dlogits (V <= 32).  scratch: B * sdpl_scratch_floats(T)
-// floats; *err |= 1 when a pseudo-label transcript holds a special token (the reference raises).
-long sdpl_scratch_floats(int T);
+// SUTA loss / gradient already in loss / dlogits.  scratch: B * sdpl_scratch_floats(T, V) floats (enough for
+// either path).  tab == null: the 32-letter kernels (V <= 32, the 960h rule); otherwise the any-vocabulary
+// kernels (V <= SUTA_MAX_VOCAB, T <= 2048) with the pseudo-label table in device memory: class id i expands to
+// ids[off[i] .. off[i + 1]) (each in [1, V)) when kind[i] is NORMAL, to nothing when DROP (the pad token), to
+// a space when SPACE (the word delimiter: stripped at both ends, space_id inside, a lookup failure when
+// space_id < 0) and fails the reference's vocab lookup when FAIL.
+// *err |= SDPL_FLAG_LOOKUP when a pseudo-label transcript holds a character that is no token (the reference
+// raises KeyError), |= SDPL_FLAG_INFEASIBLE when the target admits no alignment in T frames (torch: inf loss,
+// NaN gradient); the wide path then computes with an empty target, so nothing non-finite is written.
+enum { SDPL_KIND_NORMAL = 0, SDPL_KIND_DROP = 1, SDPL_KIND_SPACE = 2, SDPL_KIND_FAIL = 3 };
+enum { SDPL_FLAG_LOOKUP = 1, SDPL_FLAG_INFEASIBLE = 2 };
+struct SdplTable {
+    const int* off;   // [V + 1]
+    const int* ids;   // [off[V]]
+    const int* kind;  // [V]
+    int space_id;
+};
+long sdpl_scratch_floats(int T, int V);
 void launch_sdpl_loss(const float* logits, int B, int T, int V, float pl_coef, const int* tlen, float* dlogits,
-                      float* loss, float* scratch, int* err, hipStream_t st);
+                      float* loss, float* scratch, int* err, const SdplTable* tab, hipStream_t st);
 
 // Argmax ids per frame (first max, like torch.argmax): a row per thread for V <= 64, a wave per row above.
 void launch_argmax(const float* logits, long rows, int V, int* ids, hipStream_t st);

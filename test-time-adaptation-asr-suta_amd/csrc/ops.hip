@@ -2252,6 +2252,8 @@ void suta_latch_switches() {
     s.loss_wide = (lw && atoi(lw) != 0) ? 1 : 0;
     const char* f32p = std::getenv("SUTA_F32P");
     s.f32p = f32p ? std::min(2, std::max(0, atoi(f32p))) : 1;
+    const char* sw = std::getenv("SUTA_SDPL_WIDE");
+    s.sdpl_wide = (sw && atoi(sw) != 0) ? 1 : 0;
     s.latched = 1;
     g_switches = s;
 }

@@ -13,7 +13,11 @@
 //             the extended-target states s with label c of alpha_t(s) beta_t(s); the exp(lp) term
 //             assumes lp is normalised over classes, which it is not here -- reproduced as is
 //   dL/dz   = through the time log-softmax: g - softmax_t(z)[t,c] * sum_t' g[t',c]
-// Kernels: (1) per utterance (one block): greedy ids, target, time log-softmax, the alpha and beta
+// Two paths.  The 32-letter path below (V <= 32, the 960h rule, no table: ids 1..3 fail, 4 is the delimiter)
+// and, further down, the any-vocabulary path, which follows a checkpoint's own vocab.json through a
+// pseudo-label table (suta_set_pseudo_labels) and runs every other case (above 32 classes the engine
+// refuses SDPL until such a table is set).
+// Kernels of the 32-letter path: (1) per utterance (one block): greedy ids, target, time log-softmax, the alpha and beta
 // recursions in log space (fp32, torch's 3-term max-shifted log-sum-exp); (2) one thread per
 // (frame, class): posterior occupancy and dL/dlp; (3) per utterance: the time-softmax backward and
 // the (1 - pl, pl) mix into the SUTA gradient and loss already in dlogits / loss.  Fixed-order sums
@@ -237,16 +241,323 @@ __global__ __launch_bounds__(256) void sdpl_combine_kernel(int Tl, int V, float 
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Any-vocabulary path (V <= SUTA_MAX_VOCAB, a pseudo-label table, T <= SD_MAXT): six launches.
+//   argmax        greedy ids of every frame (ops.hip launch_argmax: a wave per row above 64 classes, first max)
+//   wide_lz       lz[c] = log sum_t exp(z[t][c]): a block per (64-class chunk, utterance), lanes along classes so a
+//                 row read is contiguous, the time axis over SDW_PART waves combined in wave order; lp = z - lz is
+//                 recomputed where it is used instead of stored as a [T][V] plane
+//   wide_target   per utterance: collapse repeats, expand every id through the table (dropped / space / lookup
+//                 failure / its characters' ids), strip leading and trailing spaces, map inner spaces, check that the
+//                 alignment is feasible (U + adjacent repeats <= T), and counting-sort the target positions by class
+//   wide_ab       the alpha / beta recursions as sdpl_prep_kernel's, reading lp at the blank and label classes only
+//   wide_occ0     the blank's posterior occupancy per frame (a wave per frame over the U + 1 blank states)
+//   wide_grad     a block per (64-class chunk, utterance): g = (exp(lp) - occ) / max(U, 1) with occ summed over the
+//                 class's position list in position order, Gc = sum_t g over SDW_PART waves in wave order, then the
+//                 time-softmax backward and the (1 - pl, pl) mix.  O(T (V + S)) work, fixed-order sums.
+// Padding rows t >= T_b enter no statistic; their dlogits stay as the SUTA loss kernel wrote them (0).
+// ------------------------------------------------------------------------------------------
+constexpr int SDW_PART = 16;  // waves per block of the class-chunk kernels = partial sums over time
+
+struct SdplWide {
+    float* lz;     // [V]
+    float* g;      // [Tl][V]
+    float* alpha;  // [Tl][S]
+    float* beta;   // [Tl][S]
+    float* occ0;   // [Tl]
+    int* tgt;      // [Tl]
+    int* pos;      // [Tl] target positions sorted by class (stable)
+    int* cstart;   // [V + 1] first entry of each class in pos
+    int* meta;     // [8]: U, flags, T
+    float* nll;    // [1]
+};
+
+__host__ __device__ inline long sdpl_wide_floats(int Tl, int V) {
+    const long S = 2L * Tl + 1;
+    return (long)V + (long)Tl * V + 2L * Tl * S + 3L * Tl + (V + 1) + 8 + 1 + 16;
+}
+
+__device__ __forceinline__ SdplWide sdpl_wide(float* base, int Tl, int V) {
+    const long S = 2L * Tl + 1;
+    SdplWide s;
+    s.lz = base;
+    s.g = s.lz + V;
+    s.alpha = s.g + (long)Tl * V;
+    s.beta = s.alpha + (long)Tl * S;
+    s.occ0 = s.beta + (long)Tl * S;
+    s.tgt = reinterpret_cast<int*>(s.occ0 + Tl);
+    s.pos = s.tgt + Tl;
+    s.cstart = s.pos + Tl;
+    s.meta = s.cstart + V + 1;
+    s.nll = reinterpret_cast<float*>(s.meta + 8);
+    return s;
+}
+
+__global__ __launch_bounds__(64 * SDW_PART) void sdpl_wide_lz_kernel(const float* __restrict__ logits, int Tl, int V,
+                                                                     const int* __restrict__ tlen,
+                                                                     float* __restrict__ scratch, long sstride) {
+    __shared__ float red[SDW_PART][64];
+    const int b = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lane;
+    const bool ok = c < V;
+    const int T = tlen ? tlen[b] : Tl;
+    const float* L = logits + (long)b * Tl * V + (ok ? c : 0);
+    float m = -INFINITY;
+    if (ok)
+        for (int t = w; t < T; t += SDW_PART) m = fmaxf(m, L[(long)t * V]);
+    red[w][lane] = m;
+    __syncthreads();
+    m = red[0][lane];
+#pragma unroll
+    for (int i = 1; i < SDW_PART; ++i) m = fmaxf(m, red[i][lane]);
+    __syncthreads();
+    float s = 0.f;
+    if (ok)
+        for (int t = w; t < T; t += SDW_PART) s += expf(L[(long)t * V] - m);
+    red[w][lane] = s;
+    __syncthreads();
+    if (w == 0 && ok) {
+        s = red[0][lane];
+#pragma unroll
+        for (int i = 1; i < SDW_PART; ++i) s += red[i][lane];
+        sdpl_wide(scratch + (long)b * sstride, Tl, V).lz[c] = m + logf(s);
+    }
+}
+
+__global__ __launch_bounds__(256) void sdpl_wide_target_kernel(const int* __restrict__ ids_all, int Tl, int V,
+                                                               const int* __restrict__ tlen, SdplTable tab,
+                                                               float* __restrict__ scratch, long sstride) {
+    __shared__ int tg[SD_MAXT];
+    __shared__ int cnt[SUTA_MAX_VOCAB + 1];
+    __shared__ int cur[SUTA_MAX_VOCAB];
+    __shared__ int sU;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int T = tlen ? tlen[b] : Tl;
+    const int* ids = ids_all + (long)b * Tl;
+    SdplWide sc = sdpl_wide(scratch + (long)b * sstride, Tl, V);
+    for (int c = tid; c <= V; c += 256) cnt[c] = 0;
+    __syncthreads();
+    if (tid == 0) {
+        int U = 0, prev = -1, flags = 0, spaces = 0;
+        bool full = false;
+        auto push = [&](int v) {  // a feasible target has U <= T <= SD_MAXT labels
+            if (U >= T) full = true;
+            else tg[U++] = v;
+        };
+        for (int t = 0; t < T && !full; ++t) {
+            const int i = ids[t];
+            if (i == prev) continue;
+            prev = i;
+            const int k = tab.kind[i];
+            if (k == SDPL_KIND_DROP) continue;
+            if (k == SDPL_KIND_FAIL) {
+                flags |= SDPL_FLAG_LOOKUP;
+                continue;
+            }
+            if (k == SDPL_KIND_SPACE) {  // strip(): kept only between two labels
+                if (U > 0) ++spaces;
+                continue;
+            }
+            const int q0 = tab.off[i], q1 = tab.off[i + 1];
+            if (q1 > q0) {
+                for (; spaces > 0 && !full; --spaces) {
+                    if (tab.space_id < 0) flags |= SDPL_FLAG_LOOKUP;
+                    else push(tab.space_id);
+                }
+                spaces = 0;
+            }
+            for (int q = q0; q < q1 && !full; ++q) push(tab.ids[q]);
+        }
+        int rep = 0;
+        for (int j = 1; j < U; ++j) rep += tg[j] == tg[j - 1];
+        if (full || U + rep > T) flags |= SDPL_FLAG_INFEASIBLE;
+        if (flags) U = 0;  // the engine raises after the call; the kernels below stay in bounds and finite
+        for (int j = 0; j < U; ++j) ++cnt[tg[j] + 1];
+        for (int c = 0; c < V; ++c) {
+            cnt[c + 1] += cnt[c];
+            cur[c] = cnt[c];
+        }
+        for (int j = 0; j < U; ++j) sc.pos[cur[tg[j]]++] = j;
+        sU = U;
+        sc.meta[0] = U;
+        sc.meta[1] = flags;
+        sc.meta[2] = T;
+    }
+    __syncthreads();
+    const int U = sU;
+    for (int j = tid; j < U; j += 256) sc.tgt[j] = tg[j];
+    for (int c = tid; c <= V; c += 256) sc.cstart[c] = cnt[c];
+}
+
+__global__ __launch_bounds__(256) void sdpl_wide_ab_kernel(const float* __restrict__ logits, int Tl, int V,
+                                                           float* __restrict__ scratch, long sstride) {
+    __shared__ int tg[SD_MAXT];
+    __shared__ float lzt[SD_MAXT];
+    __shared__ float rowa[2 * SD_MAXT + 1], rowb[2 * SD_MAXT + 1];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* L = logits + (long)b * Tl * V;
+    SdplWide sc = sdpl_wide(scratch + (long)b * sstride, Tl, V);
+    const int U = sc.meta[0], T = sc.meta[2], S = 2 * U + 1;
+    const float lz0 = sc.lz[0];
+    for (int j = tid; j < U; j += 256) {
+        const int c = sc.tgt[j];
+        tg[j] = c;
+        lzt[j] = sc.lz[c];
+    }
+    __syncthreads();
+    auto lab = [&](int s) { return (s & 1) ? tg[s >> 1] : 0; };
+    auto lp = [&](int t, int s) {  // log-softmax over time at the state's class
+        return (s & 1) ? L[(long)t * V + tg[s >> 1]] - lzt[s >> 1] : L[(long)t * V] - lz0;
+    };
+    for (int s = tid; s < S; s += 256) {
+        const float v = s < 2 ? lp(0, s) : -INFINITY;
+        rowa[s] = v;
+        sc.alpha[s] = v;
+    }
+    __syncthreads();
+    float* prev = rowa;
+    float* cur = rowb;
+    for (int t = 1; t < T; ++t) {
+        for (int s = tid; s < S; s += 256) {
+            const int l = lab(s);
+            const float a1 = prev[s];
+            const float a2 = s > 0 ? prev[s - 1] : -INFINITY;
+            const float a3 = (s > 1 && l != 0 && l != lab(s - 2)) ? prev[s - 2] : -INFINITY;
+            const float v = lse3(a1, a2, a3) + lp(t, s);
+            cur[s] = v;
+            sc.alpha[(long)t * S + s] = v;
+        }
+        __syncthreads();
+        float* tmp = prev;
+        prev = cur;
+        cur = tmp;
+    }
+    if (tid == 0) {
+        const float l1 = prev[S - 1];
+        const float l2 = S > 1 ? prev[S - 2] : -INFINITY;
+        sc.nll[0] = -lse2(l1, l2);
+    }
+    __syncthreads();
+    for (int s = tid; s < S; s += 256) {
+        const float v = (s == S - 1 || s == S - 2) ? lp(T - 1, s) : -INFINITY;
+        rowa[s] = v;
+        sc.beta[(long)(T - 1) * S + s] = v;
+    }
+    __syncthreads();
+    prev = rowa;
+    cur = rowb;
+    for (int t = T - 2; t >= 0; --t) {
+        for (int s = tid; s < S; s += 256) {
+            const int l = lab(s);
+            const float b1 = prev[s];
+            const float b2 = s < S - 1 ? prev[s + 1] : -INFINITY;
+            const float b3 = (s < S - 2 && l != 0 && l != lab(s + 2)) ? prev[s + 2] : -INFINITY;
+            const float v = lse3(b1, b2, b3) + lp(t, s);
+            cur[s] = v;
+            sc.beta[(long)t * S + s] = v;
+        }
+        __syncthreads();
+        float* tmp = prev;
+        prev = cur;
+        cur = tmp;
+    }
+}
+
+// occ0[t] = sum over the blank states s = 0, 2, .., 2U of exp(alpha + beta + nll - lp[t][0])
+__global__ __launch_bounds__(256) void sdpl_wide_occ0_kernel(const float* __restrict__ logits, int Tl, int V,
+                                                             float* __restrict__ scratch, long sstride) {
+    const int b = blockIdx.y, lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    SdplWide sc = sdpl_wide(scratch + (long)b * sstride, Tl, V);
+    const int U = sc.meta[0], T = sc.meta[2], S = 2 * U + 1;
+    if (t >= T) return;
+    const float lp = logits[((long)b * Tl + t) * V] - sc.lz[0], nll = sc.nll[0];
+    const float* al = sc.alpha + (long)t * S;
+    const float* be = sc.beta + (long)t * S;
+    float occ = 0.f;
+    for (int j = lane; j <= U; j += 64) occ += expf(al[2 * j] + be[2 * j] + nll - lp);
+    occ = wave_sum(occ);
+    if (lane == 0) sc.occ0[t] = occ;
+}
+
+__global__ __launch_bounds__(64 * SDW_PART) void sdpl_wide_grad_kernel(const float* __restrict__ logits, int Tl, int V,
+                                                                       float pl, float* __restrict__ dlogits,
+                                                                       float* __restrict__ loss,
+                                                                       float* __restrict__ scratch, long sstride,
+                                                                       int* __restrict__ err) {
+    __shared__ float red[SDW_PART][64];
+    const int b = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lane;
+    const bool ok = c < V;
+    SdplWide sc = sdpl_wide(scratch + (long)b * sstride, Tl, V);
+    const int U = sc.meta[0], T = sc.meta[2], S = 2 * U + 1;
+    const float un = (float)max(U, 1), nll = sc.nll[0];
+    const float* L = logits + (long)b * Tl * V;
+    float lzc = 0.f, gs = 0.f;
+    if (ok) {
+        lzc = sc.lz[c];
+        const int q0 = sc.cstart[c], q1 = sc.cstart[c + 1];
+        for (int t = w; t < T; t += SDW_PART) {
+            const float lp = L[(long)t * V + c] - lzc;
+            float occ = 0.f;
+            if (c == 0) {
+                occ = sc.occ0[t];
+            } else {
+                const float* al = sc.alpha + (long)t * S;
+                const float* be = sc.beta + (long)t * S;
+                for (int q = q0; q < q1; ++q) {
+                    const int s = 2 * sc.pos[q] + 1;
+                    occ += expf(al[s] + be[s] + nll - lp);
+                }
+            }
+            const float g = (expf(lp) - occ) / un;
+            sc.g[(long)t * V + c] = g;
+            gs += g;
+        }
+    }
+    red[w][lane] = gs;
+    __syncthreads();
+    float Gc = red[0][lane];
+#pragma unroll
+    for (int i = 1; i < SDW_PART; ++i) Gc += red[i][lane];
+    if (ok) {
+        float* dL = dlogits + (long)b * Tl * V;
+        const float keep = 1.0f - pl;
+        for (int t = w; t < T; t += SDW_PART) {  // each thread reads back the g it wrote
+            const long k = (long)t * V + c;
+            const float dz = sc.g[k] - expf(L[k] - lzc) * Gc;
+            dL[k] = keep * dL[k] + pl * dz;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        loss[b] = (1.0f - pl) * loss[b] + pl * (nll / un);
+        if (sc.meta[1]) atomicOr(err, sc.meta[1]);
+    }
+}
+
 }  // namespace
 
-long sdpl_scratch_floats(int Tl) {
+long sdpl_scratch_floats(int Tl, int V) {
     const long S = 2L * Tl + 1;
-    return 64L * Tl + 2L * Tl * S + Tl + 4 + 1 + 16;
+    const long legacy = 64L * Tl + 2L * Tl * S + Tl + 4 + 1 + 16;
+    return std::max(legacy, sdpl_wide_floats(Tl, V)) + Tl;  // + the utterance's share of the greedy-id array
 }
 
 void launch_sdpl_loss(const float* logits, int B, int Tl, int V, float pl_coef, const int* tlen, float* dlogits,
-                      float* loss, float* scratch, int* err, hipStream_t st) {
-    const long ss = sdpl_scratch_floats(Tl);
+                      float* loss, float* scratch, int* err, const SdplTable* tab, hipStream_t st) {
+    const long ss = sdpl_scratch_floats(Tl, V) - Tl;  // B per-utterance blocks, then the greedy ids [B][Tl]
+    if (tab) {
+        int* ids_all = reinterpret_cast<int*>(scratch + (long)B * ss);
+        const dim3 cgrid((V + 63) / 64, B);
+        launch_argmax(logits, (long)B * Tl, V, ids_all, st);
+        hipLaunchKernelGGL(sdpl_wide_lz_kernel, cgrid, dim3(64 * SDW_PART), 0, st, logits, Tl, V, tlen, scratch, ss);
+        hipLaunchKernelGGL(sdpl_wide_target_kernel, dim3(B), dim3(256), 0, st, ids_all, Tl, V, tlen, *tab, scratch, ss);
+        hipLaunchKernelGGL(sdpl_wide_ab_kernel, dim3(B), dim3(256), 0, st, logits, Tl, V, scratch, ss);
+        hipLaunchKernelGGL(sdpl_wide_occ0_kernel, dim3((Tl + 3) / 4, B), dim3(256), 0, st, logits, Tl, V, scratch, ss);
+        hipLaunchKernelGGL(sdpl_wide_grad_kernel, cgrid, dim3(64 * SDW_PART), 0, st, logits, Tl, V, pl_coef, dlogits,
+                           loss, scratch, ss, err);
+        return;
+    }
     hipLaunchKernelGGL(sdpl_prep_kernel, dim3(B), dim3(256), 0, st, logits, Tl, V, tlen, scratch, ss);
     hipLaunchKernelGGL(sdpl_grad_kernel, dim3((unsigned)((Tl * 32L + 255) / 256), B), dim3(256), 0, st, Tl, scratch,
                        ss);

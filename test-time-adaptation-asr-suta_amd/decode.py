@@ -97,6 +97,110 @@ def ctc_decode(ids: Sequence[int], vocab=VOCAB) -> str:
     return "".join(out).strip()
 
 
+# pseudo-label table kinds (csrc/ops.h SDPL_KIND_*)
+KIND_NORMAL, KIND_DROP, KIND_SPACE, KIND_FAIL = 0, 1, 2, 3
+
+
+class PseudoLabelTable:
+    """How every class id of a vocabulary enters the SDPL pseudo-label target (main_SDPL.py:194-203):
+    offsets (V + 1) and ids: id i expands to ids[offsets[i]:offsets[i + 1]]; kinds (V): KIND_NORMAL (its characters'
+    ids), KIND_DROP (the pad token), KIND_SPACE (the word delimiter) or KIND_FAIL (a character of the token is no
+    token: the reference's vocab lookup raises KeyError); space_id: what a space inside the transcript maps to
+    (vocab['|'], the literal bar the reference hard-codes), -1 when vocab.json has no '|'; notice: a warning for the
+    user, or None."""
+
+    def __init__(self, offsets, ids, kinds, space_id, notice=None):
+        self.offsets, self.ids, self.kinds, self.space_id, self.notice = offsets, ids, kinds, space_id, notice
+
+
+def _as_vocab(vocab) -> CTCVocab:
+    return vocab if isinstance(vocab, CTCVocab) else CTCVocab(list(vocab), pad_token=vocab[PAD_ID])
+
+
+def pseudo_label_table(vocab) -> PseudoLabelTable:
+    """The pseudo-label table of a CTCVocab (or a token list with pad = id 0, delimiter '|').
+
+    The reference decodes the greedy ids with processor.batch_decode and maps every character of that string
+    through vocab.json, a space as '|' (main_SDPL.py:197-202).  Per class id that is: the pad token gives nothing,
+    the word delimiter a space (strip() removes those at both ends of the utterance), any other token the ids of
+    its characters.  Raises ValueError for a vocabulary this cannot express exactly: a token other than the
+    delimiter that contains whitespace (strip() and the ' ' -> '|' rule would then act inside tokens), an
+    expansion that contains id 0 (nn.CTCLoss(blank=0) would read the label as blank), or two ids that decode to the
+    same string and could be grouped by the tokenizer while the engine groups by id."""
+    v = _as_vocab(vocab)
+    toks = v.tokens
+    index = {}
+    for i, t in enumerate(toks):
+        index.setdefault(t, i)
+    offsets, ids, kinds = [0], [], []
+    for i, t in enumerate(toks):
+        kind = KIND_NORMAL
+        if t == v.pad_token:
+            kind = KIND_DROP
+        elif t == v.word_delimiter_token:
+            kind = KIND_SPACE
+        else:
+            if any(ch.isspace() for ch in t):
+                raise ValueError(f"token {t!r} (id {i}) contains whitespace: the reference strips the decoded string "
+                                 "and maps every space to '|' (main_SDPL.py:197-202), which a per-token table "
+                                 "cannot express")
+            exp = [index.get(ch, -1) for ch in t]
+            if any(e < 0 for e in exp):
+                kind = KIND_FAIL
+            elif 0 in exp:
+                raise ValueError(f"token {t!r} (id {i}) expands to id 0 ({toks[0]!r}), which nn.CTCLoss(blank=0) "
+                                 "reads as the blank (main_SDPL.py:195)")
+            else:
+                ids.extend(exp)
+        kinds.append(kind)
+        offsets.append(len(ids))
+    for i, t in enumerate(toks):
+        if index[t] != i and not (kinds[i] == KIND_FAIL and kinds[index[t]] == KIND_FAIL):
+            raise ValueError(f"ids {index[t]} and {i} both decode to {t!r}: the tokenizer groups repeats by string, "
+                             "the engine by id")
+    space_id = index.get(WORD_DELIM, -1)
+    if space_id == 0:
+        raise ValueError(f"'{WORD_DELIM}' is id 0: a space inside the transcript would become the CTC blank "
+                         "(main_SDPL.py:195, 200-202)")
+    notice = None
+    if v.pad_id != PAD_ID:
+        where = f"id {v.pad_id}" if v.pad_id is not None else "not in vocab.json"
+        notice = (f"[suta_amd] pad token '{v.pad_token}' is {where}, but the pseudo-label CTC loss uses id {PAD_ID} "
+                  f"({toks[PAD_ID]!r}) as its blank as the reference hard-codes it (main_SDPL.py:195)")
+    return PseudoLabelTable(offsets, ids, kinds, space_id, notice)
+
+
+def pseudo_label_target(ids: Sequence[int], vocab=VOCAB) -> List[int]:
+    """The reference's pseudo-label target of a greedy id row for any vocabulary (main_SDPL.py:196-202 on
+    Wav2Vec2CTCTokenizer.batch_decode): group repeats, drop pad, expand every token to its characters' ids,
+    the delimiter to a space, strip the spaces at both ends, map the inner ones to vocab['|'].  KeyError where the
+    reference's lookup fails."""
+    tab = vocab if isinstance(vocab, PseudoLabelTable) else pseudo_label_table(vocab)
+    out: List[int] = []   # -1 = a space
+    prev = None
+    for i in ids:
+        i = int(i)
+        if i == prev:
+            continue
+        prev = i
+        k = tab.kinds[i]
+        if k == KIND_DROP:
+            continue
+        if k == KIND_FAIL:
+            raise KeyError(f"id {i}: a character of the token is not in the vocabulary (reference vocab lookup fails)")
+        if k == KIND_SPACE:
+            out.append(-1)
+        else:
+            out.extend(tab.ids[tab.offsets[i]:tab.offsets[i + 1]])
+    while out and out[0] == -1:
+        out.pop(0)
+    while out and out[-1] == -1:
+        out.pop()
+    if -1 in out and tab.space_id < 0:
+        raise KeyError(f"'{WORD_DELIM}' is not in the vocabulary (reference vocab lookup of a space fails)")
+    return [tab.space_id if o == -1 else o for o in out]
+
+
 def batch_decode(ids: np.ndarray, vocab=VOCAB) -> List[str]:
     ids = np.asarray(ids)
     if ids.ndim == 1:

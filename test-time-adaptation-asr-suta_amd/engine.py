@@ -19,7 +19,7 @@ MAX_CONV = 8
 
 # exported symbols (kept in sync with include/suta.h; tests/test_abi.py checks both)
 EXPORTS = ("suta_create", "suta_destroy", "suta_reset", "suta_num_frames", "suta_forward", "suta_step", "suta_step_ex",
-           "suta_adapt", "suta_adapt_varlen", "suta_loss_grad", "suta_get_param", "suta_param_info", "suta_sync", "suta_stream", "suta_set_timing",
+           "suta_adapt", "suta_adapt_varlen", "suta_loss_grad", "suta_set_pseudo_labels", "suta_get_param", "suta_param_info", "suta_sync", "suta_stream", "suta_set_timing",
            "suta_get_timing", "suta_get_timing_ex", "suta_set_precision", "suta_set_graphs", "suta_set_census",
            "suta_get_census", "suta_get_graph_stats", "suta_last_error")
 
@@ -105,6 +105,7 @@ def load_library(path: str = LIB_PATH):
                                P(HParamsC), i32p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, i64p]
     lib.suta_loss_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, P(HParamsC), C.c_void_p,
                                    C.c_void_p]
+    lib.suta_set_pseudo_labels.argtypes = [C.c_void_p, i32p, i32p, i32p, C.c_int32]
     lib.suta_get_param.argtypes = [C.c_void_p, C.c_int32, C.c_char_p, f32p, C.c_int64]
     lib.suta_param_info.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, i32p, i64p]
     lib.suta_sync.argtypes = [C.c_void_p]
@@ -315,6 +316,24 @@ class SutaEngine:
         _check(self.lib.suta_loss_grad(self.handle, _ptr(a), a.shape[0], a.shape[1], C.byref(hp.to_c()), _ptr(d),
                                        _ptr(loss)))
         return d, loss
+
+    def set_pseudo_labels(self, vocab=None):
+        """The SDPL pseudo labels follow `vocab` (a decode.CTCVocab, a token list, or a decode.PseudoLabelTable;
+        suta_set_pseudo_labels); None takes the table away: the built-in 32-letter rule up to 32 classes,
+        SDPL refused above.  ValueError for a vocabulary the table
+        cannot express (decode.pseudo_label_table).  Returns the table's notice for the user, or None."""
+        if vocab is None:
+            _check(self.lib.suta_set_pseudo_labels(self.handle, None, None, None, -1))
+            return None
+        from .decode import PseudoLabelTable, pseudo_label_table
+        tab = vocab if isinstance(vocab, PseudoLabelTable) else pseudo_label_table(vocab)
+        if len(tab.kinds) != self.V:
+            raise ValueError(f"vocabulary of {len(tab.kinds)} tokens on an engine of vocab_size {self.V}")
+        off = (C.c_int32 * len(tab.offsets))(*tab.offsets)
+        ids = (C.c_int32 * max(1, len(tab.ids)))(*tab.ids)
+        kinds = (C.c_int32 * len(tab.kinds))(*tab.kinds)
+        _check(self.lib.suta_set_pseudo_labels(self.handle, off, ids, kinds, int(tab.space_id)))
+        return tab.notice
 
     def get_param(self, slot: int, name: str) -> np.ndarray:
         shape = self.shapes[name]

@@ -144,12 +144,14 @@ def resolve_scheduler(name):
     return 1, 0.7
 
 
-def workspace_bytes_per_audio_s(cfg) -> float:
+def workspace_bytes_per_audio_s(cfg, sdpl: bool = False) -> float:
     """Upper estimate of the engine's device workspace per second of padded audio in a batch (DESIGN.md section 2:
     measured 0.36 GB per 8 s base utterance = 45 MB/s): 50 frames/s x 4 B x layers x 14 H saved per frame in the
     encoder, plus ~3 fp32 buffers of the conv stack's 512 channels over its ~6350 frames per second."""
     V = cfg.get("vocab_size", 32)
     head = 50 * 4 * (2 * V + 66)   # logits, dlogits and the loss scratch per frame (larger vocabularies count)
+    if sdpl:
+        head += 50 * 4 * V         # the SDPL gradient plane g[T][V] (its alpha / beta planes grow with T^2: 2.6 MB at 8 s)
     return 50 * 4 * cfg["num_hidden_layers"] * 14 * cfg["hidden_size"] + 6350 * 512 * 4 * 3 + head
 
 
@@ -166,12 +168,12 @@ def engine_fixed_bytes(cfg, weights, max_batch: int, precision: str = "fp32") ->
     return wbytes * (2.0 if precision == "bf16" else 1.0) + 4.0 * pn * (4 * max_batch + 1)
 
 
-def clamp_budget(budget_s: float, cfg, free_bytes, frac: float = 0.7) -> float:
+def clamp_budget(budget_s: float, cfg, free_bytes, frac: float = 0.7, sdpl: bool = False) -> float:
     """The ragged-batch audio budget limited to `frac` of the device's free memory (the defaults are sized for the
     288 GB of an MI355X; a smaller GPU would otherwise fail its first allocation)."""
     if not free_bytes:
         return budget_s
-    return max(1.0, min(budget_s, frac * free_bytes / workspace_bytes_per_audio_s(cfg)))
+    return max(1.0, min(budget_s, frac * free_bytes / workspace_bytes_per_audio_s(cfg, sdpl)))
 
 
 def exp_name_of(a, sdpl: bool = False) -> str:
@@ -244,9 +246,20 @@ def main(argv=None, sdpl: bool = False):
     from .synth import normalize
 
     exp_name = exp_name_of(a, sdpl)
+    vocab = pl_table = None
+    if os.path.isfile(os.path.join(a.asr, "vocab.json")):   # --asr <local dir>: its own vocabulary (presets: built in)
+        from .decode import load_vocab
+        vocab = load_vocab(a.asr)
     if sdpl:
-        from .decode import VOCAB
-        say({t: i for i, t in enumerate(VOCAB)})  # main_SDPL.py:269-271 prints vocab.json
+        # main_SDPL.py:269-271 prints vocab.json: the reference opens the 960h table in its working directory; the
+        # checkpoint's own is the one consistent reading for any other checkpoint
+        from .decode import VOCAB, pseudo_label_table
+        say({t: i for i, t in enumerate(vocab.tokens if vocab is not None else VOCAB)})
+        if vocab is not None:
+            try:
+                pl_table = pseudo_label_table(vocab)
+            except ValueError as err:
+                raise SystemExit(f"--asr {a.asr}: the SDPL pseudo labels cannot follow this vocabulary: {err}")
     subsets = [x for x in a.chime_subsets.split(",") if x] if a.chime_subsets else None
     dataset = load_dataset(a.split, a.dataset_name, a.dataset_dir, a.batch_size, a.extra_noise,
                            chime_subsets=subsets)
@@ -261,10 +274,9 @@ def main(argv=None, sdpl: bool = False):
         say(line)
 
     cfg, weights = load_model(a.asr, a.synthetic_weights)
-    if os.path.isfile(os.path.join(a.asr, "vocab.json")):   # --asr <local dir>: its own vocabulary (presets: built in)
+    if vocab is not None:
         import functools
-        from .decode import blank_notice, load_vocab
-        vocab = load_vocab(a.asr)
+        from .decode import blank_notice
         batch_decode = functools.partial(batch_decode, vocab=vocab)
         note = blank_notice(vocab)
         if note and rank == 0:
@@ -285,7 +297,7 @@ def main(argv=None, sdpl: bool = False):
     if torch.cuda.is_available():
         # the engines' fixed footprint (weights, bf16 weight planes, per-slot state) comes off the free memory first
         free = torch.cuda.mem_get_info(device)[0] - n_eng * engine_fixed_bytes(cfg, weights, gb, a.precision)
-        budget = clamp_budget(a.gpu_budget_s, cfg, max(1.0, free), frac=0.7 / n_eng)
+        budget = clamp_budget(a.gpu_budget_s, cfg, max(1.0, free), frac=0.7 / n_eng, sdpl=sdpl)
         if budget < a.gpu_budget_s:
             say(f"[suta_amd] --gpu_budget_s {a.gpu_budget_s} x {n_eng} engine(s) exceeds 70 % of the free device "
                 f"memory; using {budget:.0f} s")
@@ -293,6 +305,10 @@ def main(argv=None, sdpl: bool = False):
     engines = [SutaEngine(cfg, weights, device=device, max_batch=gb) for _ in range(n_eng)]
     for e in engines:
         e.set_precision(a.precision)
+        if pl_table is not None:
+            e.set_pseudo_labels(pl_table)
+    if pl_table is not None and pl_table.notice and rank == 0:
+        print(pl_table.notice, file=sys.stderr)
     engine = engines[0]
     hp = SutaHParams(lr=a.lr, temp=a.temp, em_coef=a.em_coef, div_coef=0.0 if sdpl else a.div_coef,
                      reweight=a.reweight, non_blank=a.non_blank, train_feature=a.train_feature,
