@@ -54,9 +54,9 @@ typedef struct suta_engine suta_engine;
 
 /* HF Wav2Vec2Config fields that determine the arithmetic (configuration_wav2vec2.py:165-219). */
 typedef struct suta_model_config {
-    int32_t hidden_size;                   /* 768 base, 1024 large */
+    int32_t hidden_size;                   /* 768 base, 1024 large, 1280 / 1920 XLS-R 1B / 2B; <= 2048 */
     int32_t num_hidden_layers;             /* 12 / 24 */
-    int32_t num_attention_heads;           /* 12 / 16 */
+    int32_t num_attention_heads;           /* 12 / 16; head dim 64 and 72 .. 128 (% 8) run flash attention */
     int32_t intermediate_size;             /* 3072 / 4096 */
     int32_t vocab_size;                    /* 32; 1 .. 1024 */
     int32_t num_conv_layers;               /* 7 */
@@ -275,6 +275,11 @@ int32_t suta_set_graphs(suta_engine* e, int32_t enable);
 #define SUTA_LOOP_CAPTURED 1
 #define SUTA_LOOP_REPLAYED 2
 int32_t suta_get_graph_stats(suta_engine* e, int32_t* last_mode_out, int64_t* captures_out, int64_t* launches_out);
+
+/* Device bytes of the workspace planned for the current batch layout (0 before the first call that sets one):
+ * activations saved for the backward, scratch and gradients; instrumentation, no reference counterpart.  Tests pin
+ * with it that a geometry on the flash attention kernels holds no T x T probability matrices. */
+int32_t suta_get_workspace_bytes(suta_engine* e, int64_t* bytes_out);
 
 const char* suta_last_error(void);
 

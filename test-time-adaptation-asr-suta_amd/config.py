@@ -21,10 +21,19 @@ _BASE = dict(
 _LARGE = dict(_BASE, hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, intermediate_size=4096,
               conv_bias=True, feat_extract_norm="layer", do_stable_layer_norm=True)
 
+# XLS-R 1B / 2B (facebook/wav2vec2-xls-r-1b, -2b and their CTC fine-tunes): head dims 80 / 120, positional-conv
+# groups of width 80 / 120.  vocab_size is the fine-tune's; a checkpoint directory's config.json governs.
+_XLSR_1B = dict(_LARGE, hidden_size=1280, num_hidden_layers=48, num_attention_heads=16, intermediate_size=5120)
+_XLSR_2B = dict(_LARGE, hidden_size=1920, num_hidden_layers=48, num_attention_heads=16, intermediate_size=7680)
+
 # Tiny geometries used for the committed golden vectors (tests/golden/make_golden.py).
 _TINY_GROUP = dict(_BASE, hidden_size=64, num_hidden_layers=2, num_attention_heads=4, intermediate_size=128,
                    conv_dim=[32] * 7, num_conv_pos_embeddings=16, num_conv_pos_embedding_groups=4)
 _TINY_LAYER = dict(_TINY_GROUP, conv_bias=True, feat_extract_norm="layer", do_stable_layer_norm=True)
+# head dims 80 / 120 (the XLS-R 1B / 2B head and positional-conv group widths) at test size
+_TINY_HD80 = dict(_TINY_LAYER, hidden_size=160, num_attention_heads=2, num_conv_pos_embedding_groups=2,
+                  intermediate_size=320)
+_TINY_HD120 = dict(_TINY_HD80, hidden_size=240)
 
 PRESETS = {
     "facebook/wav2vec2-base-960h": _BASE,
@@ -32,9 +41,26 @@ PRESETS = {
     "facebook/wav2vec2-large-960h-lv60": _LARGE,
     "facebook/wav2vec2-large-960h-lv60-self": _LARGE,
     "wav2vec2-large": _LARGE,
+    "facebook/wav2vec2-xls-r-1b": _XLSR_1B,
+    "wav2vec2-xls-r-1b": _XLSR_1B,
+    "facebook/wav2vec2-xls-r-2b": _XLSR_2B,
+    "wav2vec2-xls-r-2b": _XLSR_2B,
     "tiny-group": _TINY_GROUP,
     "tiny-layer": _TINY_LAYER,
+    "tiny-hd80": _TINY_HD80,
+    "tiny-hd120": _TINY_HD120,
 }
+
+
+def head_dim(cfg: dict) -> int:
+    return cfg["hidden_size"] // cfg["num_attention_heads"]
+
+
+def flash_attention_applies(cfg: dict) -> bool:
+    """Whether the engine runs this geometry's attention on the flash kernels (no T x T matrix stored): head dim 64,
+    or 72 .. 128 in steps of 8 (csrc/attn.hip, csrc/attn_wide.hip); other head dims take the P-storing GEMM path."""
+    d = head_dim(cfg)
+    return d == 64 or (64 < d <= 128 and d % 8 == 0)
 
 
 def get_config(name_or_path: str) -> dict:

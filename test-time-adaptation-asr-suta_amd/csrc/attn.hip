@@ -1,4 +1,4 @@
-// Flash-style fused attention for head dim 64 and any T (reference: the HF Wav2Vec2Attention the
+// Flash-style fused attention for head dim 64 and any T (head dims 72 .. 128: attn_wide.hip; reference: the HF Wav2Vec2Attention the
 // SUTA loop runs, modeling_wav2vec2.py Wav2Vec2Attention.forward: softmax(q k^T * d^-1/2) v, and its
 // autograd backward).  No T x T matrix is stored: the forward keeps the per-row log-sum-exp, the
 // backward recomputes the probabilities from it.
@@ -31,14 +31,11 @@
 #include <stdexcept>
 #include <type_traits>
 
+#include "attn_common.h"
 #include "common.h"
 #include "ops.h"
 
 namespace {
-
-typedef __bf16 fbf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 fbf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // [row][64] tiles padded to 68 floats (17 16-B slots): the row reads of prod_rows (ds_read_b128, lane l32 -> row
 // l32) put row r in slot r mod 16, so each of gfx950's four 16-lane groups ({0-3,12-15,20-27}, {4-11,16-19,28-31}
@@ -46,27 +43,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // conflicts); the column reads of apply_rows stay conflict-free (32 consecutive floats per 32-lane group)
 constexpr int FA_LD = 68;
 constexpr int FA_LDT = 36;  // [64][32] transposed tiles
-
-__device__ __forceinline__ fbf16x8 cvt8(f32x4 lo, f32x4 hi) {
-    fbf16x8 v;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        v[j] = (__bf16)lo[j];
-        v[4 + j] = (__bf16)hi[j];
-    }
-    return v;
-}
-
-// accumulator register v of a 32x32 MFMA tile holds row r8(v, h) of column (lane & 31)
-__device__ __forceinline__ int r8(int v, int h) { return 8 * (v >> 2) + 4 * h + (v & 3); }
-
-// 1-D XCD-aware renumbering (cdna_hip_programming.md T1, bijective): consecutive logical blocks (the
-// query or key blocks of one head) run on one XCD and share its L2.
-__device__ __forceinline__ int xcd_block() {
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-}
 
 // The lane's 64-wide register row (the B operand of prod_rows): fp32 X[row][32h + 4m + e], m < 8;
 // bf16 X[row][16s + 8h + j], s < 4.
@@ -176,21 +152,6 @@ __device__ __forceinline__ void apply_cols(f32x16 (&o)[2], const float* __restri
         }
     }
 }
-
-// max / sum with the other half-wave's value (lane l and l ^ 32) through v_permlane32_swap (no LDS round trip, as
-// __shfl_xor's ds_bpermute is): swapping two copies of x leaves {x[l], x[l + 32]} in the lower half's pair and
-// {x[l - 32], x[l]} in the upper's, so one op of the pair is op(x[l], x[l ^ 32]) -- bitwise the shuffle form (fmax
-// and a two-term sum are commutative)
-__device__ __forceinline__ float half_swap_max(float x) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float half_swap_sum(float x) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-constexpr float LOG2E = 1.4426950408889634f;
 
 // ------------------------------------------------------------------------------------------------
 // forward: key tiles of FK = 64 (two 32-key sub-tiles: two independent S^T chains, one softmax
@@ -1608,7 +1569,10 @@ static int fb_nw() {
 // instantiations for A/B runs; from the call's switch snapshot, common.h SutaSwitches)
 static bool fb_img() { return suta_switches().flash_bf16_img != 0; }
 
-long flash_dq_scratch_floats(int B, int T, int NH) {
+bool flash_dh_ok(int dh) { return dh == 64 || flash_wide_dh(dh); }
+
+long flash_dq_scratch_floats(int B, int T, int NH, int dh) {
+    if (flash_wide_dh(dh)) return flash_wide_dq_scratch_floats(B, T, NH, dh);
     const int ng = (T + 31) / 32, nkb = (ng + fb_nw() - 1) / fb_nw();
     // the per-key-block dQ partials (row layout: T rows per head; fragment layout of the bf16-plane kernel: whole
     // 32-row query tiles)
@@ -1619,15 +1583,18 @@ long flash_dq_scratch_floats(int B, int T, int NH) {
 // kernels for A/B runs; from the call's switch snapshot)
 static bool ff_plane() { return suta_switches().flash_fwd_plane != 0; }
 
-bool flash_fwd_reads_plane(bool bf16, const void* qkvb, int H) { return bf16 && qkvb && H % 8 == 0 && ff_plane(); }
+bool flash_fwd_reads_plane(bool bf16, const void* qkvb, int H, int dh) {
+    return dh == 64 && bf16 && qkvb && H % 8 == 0 && ff_plane();
+}
 
 bool launch_flash_fwd(const float* qkv, float* ctx, float* lse, int B, int T, int NH, int H, int dh, float scale,
                       const int* tlen, bool bf16, hipStream_t st, void* ctxb_, const void* qkvb) {
+    if (flash_wide_dh(dh)) return launch_flash_wide_fwd(qkv, ctx, lse, B, T, NH, H, dh, scale, tlen, bf16, st, ctxb_);
     __bf16* ctxb = reinterpret_cast<__bf16*>(ctxb_);
     if (dh != 64 || T < 1 || H % 4) return false;
     const int ng = (T + 31) / 32, nqb = (ng + FF_NW - 1) / FF_NW;
     const dim3 grid((unsigned)((long)B * NH * nqb));
-    const bool on_plane = flash_fwd_reads_plane(bf16, qkvb, H);
+    const bool on_plane = flash_fwd_reads_plane(bf16, qkvb, H, dh);
     if (!qkv && !on_plane) throw std::invalid_argument("flash_fwd: fp32 qkv not written and the plane kernel not taken");
     if (on_plane) {
         if (reinterpret_cast<uintptr_t>(qkvb) & 15) throw std::invalid_argument("flash_fwd: bf16 qkv plane not 16-B aligned");
@@ -1688,13 +1655,15 @@ static void flash_bwd_bf16p_go(dim3 grid, hipStream_t st, const void* qkvb, cons
 // fp32-row kernels for A/B runs; from the call's switch snapshot)
 static bool fb_plane() { return suta_switches().flash_bwd_plane != 0; }
 
-bool flash_bwd_reads_planes(bool bf16, const void* qkvb, const void* dctxb, int H) {
-    return bf16 && fb_nw() == FBB_NW && qkvb && dctxb && H % 8 == 0 && fb_plane();
+bool flash_bwd_reads_planes(bool bf16, const void* qkvb, const void* dctxb, int H, int dh) {
+    return dh == 64 && bf16 && fb_nw() == FBB_NW && qkvb && dctxb && H % 8 == 0 && fb_plane();
 }
 
 bool launch_flash_bwd(const float* qkv, const float* dctx, const float* lse, const float* delta, float* dqkv,
                       float* dqp, int B, int T, int NH, int H, int dh, float scale, const int* tlen, bool bf16,
                       hipStream_t st, void* dqkvb_, const void* qkvb, const void* dctxb) {
+    if (flash_wide_dh(dh))
+        return launch_flash_wide_bwd(qkv, dctx, lse, delta, dqkv, dqp, B, T, NH, H, dh, scale, tlen, bf16, st, dqkvb_);
     __bf16* dqkvb = reinterpret_cast<__bf16*>(dqkvb_);
     if (dh != 64 || T < 1 || H % 4) return false;
     const int nw = fb_nw();
@@ -1702,7 +1671,7 @@ bool launch_flash_bwd(const float* qkv, const float* dctx, const float* lse, con
     const int nkb = (ng + nw - 1) / nw;   // key blocks per head
     const int gpb = (ng + nkb - 1) / nkb;  // key groups per block (balanced)
     const dim3 grid((unsigned)((long)B * NH * nkb));
-    const bool on_planes = flash_bwd_reads_planes(bf16, qkvb, dctxb, H);
+    const bool on_planes = flash_bwd_reads_planes(bf16, qkvb, dctxb, H, dh);
     if (!qkv && !on_planes) throw std::invalid_argument("flash_bwd: fp32 qkv not written and the plane kernel not taken");
     if (on_planes) {
         if ((reinterpret_cast<uintptr_t>(qkvb) | reinterpret_cast<uintptr_t>(dctxb)) & 15)

@@ -187,12 +187,12 @@ struct Plan {
     float *ctx, *gu, *rtmp, *logits;
     // backward
     float *dlogits, *d1, *d2, *d3, *dqkv, *dP, *dqp, *du, *dzc, *dzc2, *lnpart, *loss, *loss_scratch, *c0part, *delta;
-    bool flash = false;  // flash attention kernels (head dim 64): no T x T matrices, per-row LSE
+    bool flash = false;  // flash attention kernels (head dim 64, or 72 .. 128 in steps of 8): no T x T matrices, per-row LSE
     double* dpart;
     int* ids;
     float* splitws;
     long splitws_floats;
-    size_t bytes;
+    size_t bytes = 0;
 };
 
 }  // namespace
@@ -614,7 +614,7 @@ void suta_engine::build_plan(int B, long N) {
         pl.enc_rstd = ar.take<float>(BT);
         pl.enc_y = ar.take<float>(BT * H);
         pl.lay.assign(k.L, LayerBufs{});
-        pl.flash = attn_fused && k.H / k.NH == 64;
+        pl.flash = attn_fused && flash_dh_ok(k.H / k.NH);
         const long Psz = pl.flash ? 0 : (long)B * k.NH * T * pl.Tp;
         for (int l = 0; l < k.L; ++l) {
             LayerBufs& lb = pl.lay[l];
@@ -648,7 +648,7 @@ void suta_engine::build_plan(int B, long N) {
         pl.d3 = ar.take<float>(BT * H);
         pl.dqkv = ar.take<float>(BT * 3 * H);
         pl.dP = pl.flash ? nullptr : ar.take<float>(Psz);
-        pl.dqp = pl.flash ? ar.take<float>(flash_dq_scratch_floats(B, pl.T, k.NH)) : nullptr;
+        pl.dqp = pl.flash ? ar.take<float>(flash_dq_scratch_floats(B, pl.T, k.NH, k.H / k.NH)) : nullptr;
         pl.delta = ar.take<float>((size_t)B * k.NH * T);
         pl.du = ar.take<float>(BT * k.F);
         pl.dzc = ar.take<float>((size_t)B * maxLC);
@@ -896,10 +896,10 @@ void suta_engine::forward(int B) {
             });
             attn_in = dead ? nullptr : lb.y1;  // (dead: the QKV GEMM reads the LN1 plane only)
         }
-        void* qkvp = pl.flash ? qkv_plane(l) : nullptr;
+        void* qkvp = (pl.flash && d == 64) ? qkv_plane(l) : nullptr;  // (head dims above 64 read fp32 rows)
         // both flash kernels read qkv's bf16 plane only (the backward's dO plane is plane 2): no fp32 qkv
         const bool bf = gemm_mode == SUTA_PRECISION_BF16;
-        const bool qkv_dead = qkvp && P0 && flash_fwd_reads_plane(bf, qkvp, H) && flash_bwd_reads_planes(bf, qkvp, plane(2), H);
+        const bool qkv_dead = qkvp && P0 && flash_fwd_reads_plane(bf, qkvp, H, d) && flash_bwd_reads_planes(bf, qkvp, plane(2), H, d);
         {  // fused QKV
             GemmParams g;
             gemm_init(g);
@@ -923,14 +923,14 @@ void suta_engine::forward(int B) {
             }
             gemm(g);
         }
-        // flash attention (head dim 64, any T): ctx and the per-row LSE, no T x T matrix
+        // flash attention (head dim 64 or 72 .. 128, any T): ctx and the per-row LSE, no T x T matrix
         const bool fused = pl.flash;
         if (fused)
             timed(F_ATTN, [&] {
                 if (!launch_flash_fwd(qkv_dead ? nullptr : lb.qkv, lb.ctx, lb.lse, B, T, NH, H, d, scale, rT(),
                                       gemm_mode == SUTA_PRECISION_BF16, st, P0, qkvp))
                     throw SutaError(SUTA_ERR_UNSUPPORTED, "flash attention shape");
-            }, (double)BT * ((qkv_dead || (bf && qkvp && flash_fwd_reads_plane(bf, qkvp, H)) ? 2.0 : 4.0) * 3.0 * H +
+            }, (double)BT * ((qkv_dead || (bf && qkvp && flash_fwd_reads_plane(bf, qkvp, H, d)) ? 2.0 : 4.0) * 3.0 * H +
                             4.0 * H + (P0 && bf ? 2.0 * H : 0.0) + 4.0 * NH));  // Q, K, V read; ctx (+ plane), LSE written
         if (!fused) {
             {  // S = Q K^T * scale
@@ -1211,15 +1211,15 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
             dhres = t1;  // dhmid
         }
         // dctx = dhres @ Wo
-        void* dctxp = (pl.flash && P0) ? plane(2) : nullptr;   // dO plane of the flash backward
-        void* qkvp = (pl.flash && P0) ? qkv_plane(l) : nullptr;
+        void* dctxp = (pl.flash && P0 && d == 64) ? plane(2) : nullptr;   // dO plane of the flash backward
+        void* qkvp = (pl.flash && P0 && d == 64) ? qkv_plane(l) : nullptr;
         if (!qkvp) dctxp = nullptr;
         // softmax-backward row term delta = rowsum(dctx * ctx) per head: in the dctx GEMM's epilogue when it takes the
         // C^T-epilogue kernel and the flash backward reads the dctx plane (the fp32 dctx is then not written), else a
         // separate pass over the fp32 dctx
         bool delta_fused = false;
         if (pl.flash && dctxp && d == 64 && suta_switches().fused_delta &&
-            flash_bwd_reads_planes(gemm_mode == SUTA_PRECISION_BF16, qkvp, dctxp, H)) {
+            flash_bwd_reads_planes(gemm_mode == SUTA_PRECISION_BF16, qkvp, dctxp, H, d)) {
             GemmParams g;
             gemm_init(g);
             g.A = dhres;
@@ -1258,13 +1258,13 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
             timed(F_ATTN, [&] {
                 // (the forward's test: the fp32 qkv was not written when both flash kernels read its plane)
                 const bool bf = gemm_mode == SUTA_PRECISION_BF16;
-                const bool qkv_dead = qkvp && flash_fwd_reads_plane(bf, qkvp, H) && flash_bwd_reads_planes(bf, qkvp, dctxp, H);
+                const bool qkv_dead = qkvp && flash_fwd_reads_plane(bf, qkvp, H, d) && flash_bwd_reads_planes(bf, qkvp, dctxp, H, d);
                 if (!launch_flash_bwd(qkv_dead ? nullptr : lb.qkv, pl.ctx, lb.lse, pl.delta, dqkv_dead ? nullptr : pl.dqkv, pl.dqp, B, T,
                                       NH, H, d, scale, rT(), gemm_mode == SUTA_PRECISION_BF16, st, P1, qkvp, dctxp))
                     throw SutaError(SUTA_ERR_UNSUPPORTED, "flash attention shape");
             }, [&] {  // Q, K, V, dO, LSE, delta read; dQ, dK, dV written (fp32 and / or the bf16 plane)
                 const bool bf = gemm_mode == SUTA_PRECISION_BF16;
-                const bool planes = bf && qkvp && dctxp && flash_bwd_reads_planes(bf, qkvp, dctxp, H);
+                const bool planes = bf && qkvp && dctxp && flash_bwd_reads_planes(bf, qkvp, dctxp, H, d);
                 return (double)BT * ((planes ? 2.0 : 4.0) * 4.0 * H + 4.0 * 2.0 * NH + (dqkv_dead ? 0.0 : 12.0 * H) +
                                      (P1 && bf ? 6.0 * H : 0.0));
             }());
@@ -2008,11 +2008,13 @@ Cfg make_cfg(const suta_model_config* m) {
     c.posG = m->num_conv_pos_embedding_groups;
     c.eps = m->layer_norm_eps;
     if (c.H % c.NH || c.H % c.posG) throw SutaError(SUTA_ERR_ARG, "hidden_size not divisible by heads/groups");
-    if ((c.H / c.posG) % 16) throw SutaError(SUTA_ERR_UNSUPPORTED, "pos-conv group width must be a multiple of 16");
+    // the conv-A GEMM's segmented-K loaders move 16-B chunks (4 floats; 8 bf16 on the planes), each inside one segment
+    if ((c.H / c.posG) % 8) throw SutaError(SUTA_ERR_UNSUPPORTED, "pos-conv group width must be a multiple of 8");
     if (c.V < 1) throw SutaError(SUTA_ERR_ARG, "vocab_size < 1");
     if (c.V > SUTA_MAX_VOCAB)
         throw SutaError(SUTA_ERR_UNSUPPORTED, "vocab_size > 1024 (the loss path handles 1 <= vocab_size <= 1024)");
-    if (c.H > 1024 || c.C[c.nconv - 1] > 1024) throw SutaError(SUTA_ERR_UNSUPPORTED, "hidden > 1024");
+    if (c.H > 2048) throw SutaError(SUTA_ERR_UNSUPPORTED, "hidden > 2048");
+    if (c.C[c.nconv - 1] > 1024) throw SutaError(SUTA_ERR_UNSUPPORTED, "conv_dim > 1024");
     return c;
 }
 
@@ -2561,6 +2563,10 @@ int32_t suta_get_graph_stats(suta_engine* e, int32_t* last_mode, int64_t* captur
         if (captures) *captures = e->graph_captures;
         if (launches) *launches = e->graph_launches;
     });
+}
+
+int32_t suta_get_workspace_bytes(suta_engine* e, int64_t* bytes_out) {
+    return guard([&] { *bytes_out = (int64_t)e->plan.bytes; });
 }
 
 int32_t suta_set_census(int32_t enable) {

@@ -64,19 +64,29 @@ void launch_colsum(const float* x, int B, int rows, int C, float* out, long ostr
 // log-sum-exp lse[b][head][t] (no T x T matrix); backward recomputes P from lse and writes dQ, dK, dV
 // into dqkv's Q/K/V columns (dqp: flash_dq_scratch_floats floats of per-key-block dQ partials).
 // delta[b][head][t] = rowsum(dctx * ctx) (launch_attn_delta).  bf16: operands rounded to bf16 on the bf16
-// MFMAs (config C4).  false (nothing launched) when dh != 64.
-long flash_dq_scratch_floats(int B, int T, int NH);
+// MFMAs (config C4).  Head dim 64 runs attn.hip's kernels, head dims 64 < dh <= 128 with dh % 8 == 0 those of
+// attn_wide.hip (fp32 rows in both modes); false (nothing launched) for any other dh.
+bool flash_dh_ok(int dh);  // a head dim the flash kernels take
+long flash_dq_scratch_floats(int B, int T, int NH, int dh);
 // ctxb / dqkvb (may be null): bf16 copies of ctx / dqkv for the bf16-plane GEMMs that consume them.
 // qkv may be null when the launch takes the bf16-plane kernel (flash_*_reads_plane[s]: the engine's test for
-// leaving the fp32 qkv unwritten); the launch throws otherwise.
-bool flash_fwd_reads_plane(bool bf16, const void* qkvb, int H);
-bool flash_bwd_reads_planes(bool bf16, const void* qkvb, const void* dctxb, int H);
+// leaving the fp32 qkv unwritten); the launch throws otherwise.  The plane-reading kernels are dh = 64 only.
+bool flash_fwd_reads_plane(bool bf16, const void* qkvb, int H, int dh);
+bool flash_bwd_reads_planes(bool bf16, const void* qkvb, const void* dctxb, int H, int dh);
 bool launch_flash_fwd(const float* qkv, float* ctx, float* lse, int B, int T, int NH, int H, int dh, float scale,
                       const int* tlen, bool bf16, hipStream_t st, void* ctxb = nullptr, const void* qkvb = nullptr);
 bool launch_flash_bwd(const float* qkv, const float* dctx, const float* lse, const float* delta, float* dqkv,
                       float* dqp, int B, int T, int NH, int H, int dh, float scale, const int* tlen, bool bf16,
                       hipStream_t st, void* dqkvb = nullptr, const void* qkvb = nullptr,
                       const void* dctxb = nullptr);
+// attn_wide.hip (reached through the two launches above)
+bool flash_wide_dh(int dh);
+long flash_wide_dq_scratch_floats(int B, int T, int NH, int dh);
+bool launch_flash_wide_fwd(const float* qkv, float* ctx, float* lse, int B, int T, int NH, int H, int dh, float scale,
+                           const int* tlen, bool bf16, hipStream_t st, void* ctxb);
+bool launch_flash_wide_bwd(const float* qkv, const float* dctx, const float* lse, const float* delta, float* dqkv,
+                           float* dqp, int B, int T, int NH, int H, int dh, float scale, const int* tlen, bool bf16,
+                           hipStream_t st, void* dqkvb);
 // grouped positional conv (group width 48 or 64, exact fp32 MFMA); fwd: C = R + gelu(conv + bias), C2 = conv + bias;
 // bwd: C = conv + R (rows >= tlen -> 0).  false (nothing launched) outside the supported shapes
 bool launch_posconv(bool fwd, const float* x, const float* W, const float* bias, const float* R, float* C, float* C2,

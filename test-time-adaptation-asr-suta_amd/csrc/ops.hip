@@ -307,7 +307,7 @@ __global__ __launch_bounds__(256) void conv0_dw_reduce(const float* __restrict__
 
 
 // ------------------------------------------------------------------------------------------
-// LayerNorm over D (<= 1024): one wave per row
+// LayerNorm over D (<= 2048): one wave per row
 // ------------------------------------------------------------------------------------------
 template <int NPL>  // elements per lane = ceil(D / 64)
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ g,
@@ -369,7 +369,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
                                                             float* __restrict__ part, int nchunk,
                                                             const float* __restrict__ xin,
                                                             const float* __restrict__ meanp) {
-    __shared__ float red[4][2][NPL * 64];
+    // the block's gamma / beta partials cross LDS; D > 1024 (NPL = 32) does the two in turn through one plane
+    // (both planes at once would be the whole 64 KB of static LDS)
+    constexpr int RP = NPL <= 16 ? 2 : 1;
+    __shared__ float red[4][RP][NPL * 64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int u = blockIdx.y, ch = blockIdx.x;
     const float* gu = g + (long)u * pstride;
@@ -423,16 +426,29 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
         }
     }
     if (part) {
-#pragma unroll
-        for (int i = 0; i < NPL; ++i) {
-            red[w][0][lane + i * 64] = pg[i];
-            red[w][1][lane + i * 64] = pb[i];
-        }
-        __syncthreads();
         float* pp = part + ((long)u * nchunk + ch) * 2 * D;
-        for (int c = threadIdx.x; c < D; c += 256) {
-            pp[c] = red[0][0][c] + red[1][0][c] + red[2][0][c] + red[3][0][c];
-            pp[D + c] = red[0][1][c] + red[1][1][c] + red[2][1][c] + red[3][1][c];
+        if constexpr (RP == 2) {
+#pragma unroll
+            for (int i = 0; i < NPL; ++i) {
+                red[w][0][lane + i * 64] = pg[i];
+                red[w][1][lane + i * 64] = pb[i];
+            }
+            __syncthreads();
+            for (int c = threadIdx.x; c < D; c += 256) {
+                pp[c] = red[0][0][c] + red[1][0][c] + red[2][0][c] + red[3][0][c];
+                pp[D + c] = red[0][1][c] + red[1][1][c] + red[2][1][c] + red[3][1][c];
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NPL; ++i) red[w][0][lane + i * 64] = pg[i];
+            __syncthreads();
+            for (int c = threadIdx.x; c < D; c += 256) pp[c] = red[0][0][c] + red[1][0][c] + red[2][0][c] + red[3][0][c];
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < NPL; ++i) red[w][0][lane + i * 64] = pb[i];
+            __syncthreads();
+            for (int c = threadIdx.x; c < D; c += 256)
+                pp[D + c] = red[0][0][c] + red[1][0][c] + red[2][0][c] + red[3][0][c];
         }
     }
 }
@@ -1130,6 +1146,29 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const f32x4* __restrict
 #pragma unroll
     for (int o = G / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
     if (item < items && (g % G) == 0) {
+        const long row = item / NH;
+        const int hh = (int)(item % NH);
+        const long b = row / T, t = row % T;
+        delta[(b * NH + hh) * T + t] = s;
+    }
+}
+
+// Head dims that are no power of two (80, 120: XLS-R 1B / 2B): 32 lanes per item, the first dh / 4 of them load
+// one 16-B vector each (dh <= 128), the same lane-group reduction.
+__global__ __launch_bounds__(256) void attn_delta_pad32_kernel(const f32x4* __restrict__ dO, const f32x4* __restrict__ O,
+                                                               float* __restrict__ delta, long items, int T, int NH,
+                                                               int nv) {
+    const long g = (long)blockIdx.x * 256 + threadIdx.x;
+    const long item = g >> 5;
+    const int j = (int)(g & 31);
+    float s = 0.f;
+    if (item < items && j < nv) {
+        const f32x4 a = dO[item * nv + j], c = O[item * nv + j];
+        s = fmaf(a[3], c[3], fmaf(a[2], c[2], fmaf(a[1], c[1], a[0] * c[0])));
+    }
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (item < items && j == 0) {
         const long row = item / NH;
         const int hh = (int)(item % NH);
         const long b = row / T, t = row % T;
@@ -1883,9 +1922,14 @@ void launch_layernorm_fwd(const float* x, const float* g, const float* beta, lon
     else if (D <= 512)
         hipLaunchKernelGGL(layernorm_fwd_kernel<8>, grid, dim3(256), 0, st, x, g, beta, pstride, rows_per_utt, y, xhat,
                            rstd, rows, D, eps, gelu_out, mean);
-    else
+    else if (D <= 1024)
         hipLaunchKernelGGL(layernorm_fwd_kernel<16>, grid, dim3(256), 0, st, x, g, beta, pstride, rows_per_utt, y,
                            xhat, rstd, rows, D, eps, gelu_out, mean);
+    else if (D <= 2048)  // hidden 1280 / 1920 (XLS-R 1B / 2B)
+        hipLaunchKernelGGL(layernorm_fwd_kernel<32>, grid, dim3(256), 0, st, x, g, beta, pstride, rows_per_utt, y,
+                           xhat, rstd, rows, D, eps, gelu_out, mean);
+    else
+        throw std::invalid_argument("layernorm_fwd: D > 2048");
     if (yb && !(vec && (D == 768 || D == 1024 || D == 512))) launch_to_bf16(y, D, rows, D, yb, st);
 }
 
@@ -1931,9 +1975,14 @@ void launch_layernorm_bwd(const float* dy, const float* xhat, const float* rstd,
     else if (D <= 512)
         hipLaunchKernelGGL(layernorm_bwd_kernel<8>, grid, dim3(256), 0, st, dy, xhat, rstd, g, beta, pstride,
                            rows_per_utt, D, gelu_in, post_aux, resid, dx, pp, nchunk, x, mean);
-    else
+    else if (D <= 1024)
         hipLaunchKernelGGL(layernorm_bwd_kernel<16>, grid, dim3(256), 0, st, dy, xhat, rstd, g, beta, pstride,
                            rows_per_utt, D, gelu_in, post_aux, resid, dx, pp, nchunk, x, mean);
+    else if (D <= 2048)
+        hipLaunchKernelGGL(layernorm_bwd_kernel<32>, grid, dim3(256), 0, st, dy, xhat, rstd, g, beta, pstride,
+                           rows_per_utt, D, gelu_in, post_aux, resid, dx, pp, nchunk, x, mean);
+    else
+        throw std::invalid_argument("layernorm_bwd: D > 2048");
     if (dxb && !(vec && (D == 768 || D == 1024 || D == 512))) launch_to_bf16(dx, D, (long)B * rows_per_utt, D, dxb, st);
     if (pp)
         hipLaunchKernelGGL(chunk_reduce, dim3(cdiv(D, 256), B), dim3(256), 0, st, pp, nchunk, 2, D, dgamma, dbeta,
@@ -2317,6 +2366,12 @@ void launch_attn_delta(const float* dO, const float* O, float* delta, int B, int
         case 64: hipLaunchKernelGGL(attn_delta_kernel<16>, grid, dim3(256), 0, st, a, c, delta, items, T, NH); return;
         case 128: hipLaunchKernelGGL(attn_delta_kernel<32>, grid, dim3(256), 0, st, a, c, delta, items, T, NH); return;
         default:
+            if (dh % 4 == 0 && dh <= 128 && (reinterpret_cast<uintptr_t>(dO) & 15) == 0 &&
+                (reinterpret_cast<uintptr_t>(O) & 15) == 0) {
+                hipLaunchKernelGGL(attn_delta_pad32_kernel, dim3((unsigned)((items * 32 + 255) / 256)), dim3(256), 0, st,
+                                   a, c, delta, items, T, NH, dh / 4);
+                return;
+            }
             hipLaunchKernelGGL(attn_delta_scalar, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, dO, O, delta,
                                items, T, NH, dh);
     }

@@ -21,7 +21,7 @@ MAX_CONV = 8
 EXPORTS = ("suta_create", "suta_destroy", "suta_reset", "suta_num_frames", "suta_forward", "suta_step", "suta_step_ex",
            "suta_adapt", "suta_adapt_varlen", "suta_loss_grad", "suta_set_pseudo_labels", "suta_get_param", "suta_param_info", "suta_sync", "suta_stream", "suta_set_timing",
            "suta_get_timing", "suta_get_timing_ex", "suta_set_precision", "suta_set_graphs", "suta_set_census",
-           "suta_get_census", "suta_get_graph_stats", "suta_last_error")
+           "suta_get_census", "suta_get_graph_stats", "suta_get_workspace_bytes", "suta_last_error")
 
 
 class ModelConfigC(C.Structure):
@@ -126,6 +126,8 @@ def load_library(path: str = LIB_PATH):
     lib.suta_set_precision.argtypes = [C.c_void_p, C.c_int32]
     if hasattr(lib, "suta_get_graph_stats"):
         lib.suta_get_graph_stats.argtypes = [C.c_void_p, i32p, i64p, i64p]
+    if hasattr(lib, "suta_get_workspace_bytes"):
+        lib.suta_get_workspace_bytes.argtypes = [C.c_void_p, i64p]
     lib.suta_last_error.restype = C.c_char_p
     for name in EXPORTS:
         if name != "suta_stream" and name != "suta_last_error" and hasattr(lib, name):
@@ -394,6 +396,12 @@ class SutaEngine:
         m, c, n = C.c_int32(), C.c_int64(), C.c_int64()
         _check(self.lib.suta_get_graph_stats(self.handle, C.byref(m), C.byref(c), C.byref(n)))
         return {"last": self.LOOP_MODES[m.value], "captures": c.value, "launches": n.value}
+
+    def workspace_bytes(self) -> int:
+        """Device bytes of the workspace planned for the current batch layout (suta_get_workspace_bytes)."""
+        n = C.c_int64()
+        _check(self.lib.suta_get_workspace_bytes(self.handle, C.byref(n)))
+        return int(n.value)
 
     def set_census(self, enable: bool):
         """Start (clear) or stop the process-wide GEMM launch census (suta_set_census)."""

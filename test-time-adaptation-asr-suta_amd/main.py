@@ -144,15 +144,22 @@ def resolve_scheduler(name):
     return 1, 0.7
 
 
-def workspace_bytes_per_audio_s(cfg, sdpl: bool = False) -> float:
+def workspace_bytes_per_audio_s(cfg, sdpl: bool = False, utt_s: float = 0.0) -> float:
     """Upper estimate of the engine's device workspace per second of padded audio in a batch (DESIGN.md section 2:
     measured 0.36 GB per 8 s base utterance = 45 MB/s): 50 frames/s x 4 B x layers x 14 H saved per frame in the
-    encoder, plus ~3 fp32 buffers of the conv stack's 512 channels over its ~6350 frames per second."""
+    encoder (the FFN planes included: F = 4 H in every public config, XLS-R 1B / 2B too), plus ~3 fp32 buffers of the
+    conv stack's 512 channels over its ~6350 frames per second.  Geometries whose head dim the flash kernels take
+    (config.flash_attention_applies: XLS-R 1B / 2B included) carry no T^2 term; any other head dim stores one T x T
+    probability matrix per head and layer plus one gradient matrix, which grows with the utterance length utt_s."""
+    from .config import flash_attention_applies
     V = cfg.get("vocab_size", 32)
     head = 50 * 4 * (2 * V + 66)   # logits, dlogits and the loss scratch per frame (larger vocabularies count)
     if sdpl:
         head += 50 * 4 * V         # the SDPL gradient plane g[T][V] (its alpha / beta planes grow with T^2: 2.6 MB at 8 s)
-    return 50 * 4 * cfg["num_hidden_layers"] * 14 * cfg["hidden_size"] + 6350 * 512 * 4 * 3 + head
+    attn = 0.0
+    if not flash_attention_applies(cfg):  # P per layer and dP: NH T^2 fp32 per utterance = NH * 50 * 50 utt_s per second
+        attn = (cfg["num_hidden_layers"] + 1) * cfg["num_attention_heads"] * 50 * 50 * 4 * float(utt_s)
+    return 50 * 4 * cfg["num_hidden_layers"] * 14 * cfg["hidden_size"] + 6350 * 512 * 4 * 3 + head + attn
 
 
 def engine_fixed_bytes(cfg, weights, max_batch: int, precision: str = "fp32") -> float:
