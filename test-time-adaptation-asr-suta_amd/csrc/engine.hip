@@ -158,6 +158,99 @@ double gemm_alg_bytes(const GemmParams& p, bool a_fp32 = false) {
     return bytes;
 }
 
+// ---- GEMM descriptors: forward() and backward() describe every launch through these ----
+// One operand: base pointer, row stride, and its batch strides (s0 per z % zdiv, s1 per z / zdiv)
+struct Mat {
+    const float* p;
+    long ld;
+    long s0 = 0, s1 = 0;
+};
+// an operand with one slice per utterance (Z = B, zdiv = 1)
+inline Mat utt(const float* p, long ld, long s1) { return {p, ld, 0, s1}; }
+
+// C[z] = op(A[z]) op(B[z]) for z < Z; ta / tb: the operand is stored transposed (common.h)
+GemmParams batched(int M, int N, int K, Mat A, int ta, Mat B, int tb, Mat C, int Z, int zdiv) {
+    GemmParams g;
+    gemm_init(g);
+    g.M = M;
+    g.N = N;
+    g.K = K;
+    g.Z = Z;
+    g.zdiv = zdiv;
+    g.A = A.p;
+    g.ta = ta;
+    g.lda = A.ld;
+    g.sA0 = A.s0;
+    g.sA1 = A.s1;
+    g.B = B.p;
+    g.tb = tb;
+    g.ldb = B.ld;
+    g.sB0 = B.s0;
+    g.sB1 = B.s1;
+    g.C = const_cast<float*>(C.p);
+    g.ldc = C.ld;
+    g.sC0 = C.s0;
+    g.sC1 = C.s1;
+    return g;
+}
+// [M][K] activations times a frozen weight: x W^T (tb = 1, W [N][K]) or the input gradient dY W (tb = 0, W [K][N]).
+// Ab: bf16 plane of A written by its producer; Cb: bf16 plane of C for the next kernel (bf16 mode; null: none).
+// A / C null: the fp32 copy is not read / written (the plane is the operand)
+GemmParams linear(const float* A, const void* Ab, const float* W, int tb, float* C, void* Cb, int M, int N, int K) {
+    GemmParams g = batched(M, N, K, {A, K}, 0, {W, tb ? K : N}, tb, {C, N}, 1, 1);
+    g.Ab = Ab;
+    g.ldab = K;
+    g.Cb = Cb;
+    g.ldcb = N;
+    return g;
+}
+// epilogue operands (common.h: the order the epilogue applies them in)
+inline void add_bias(GemmParams& g, const float* b, long s0 = 0, long s1 = 0) {
+    g.epi |= EPI_BIAS;
+    g.bias = b;
+    g.sBias0 = s0;
+    g.sBias1 = s1;
+}
+inline void store_pre(GemmParams& g, Mat pre) {  // C2 = the value before GELU
+    g.epi |= EPI_STORE_PRE;
+    g.C2 = const_cast<float*>(pre.p);
+    g.ldc2 = pre.ld;
+    g.sC20 = pre.s0;
+    g.sC21 = pre.s1;
+}
+inline void set_aux(GemmParams& g, int epi, Mat aux) {  // EPI_DGELU: * gelu'(aux); EPI_SMBWD: * aux
+    g.epi |= epi;
+    g.aux = aux.p;
+    g.ldaux = aux.ld;
+    g.sAux0 = aux.s0;
+    g.sAux1 = aux.s1;
+}
+inline void set_row_vec(GemmParams& g, const float* v, long s0, long s1) {  // EPI_SMBWD: - v[m]
+    g.rowv = v;
+    g.sRow0 = s0;
+    g.sRow1 = s1;
+}
+inline void add_resid(GemmParams& g, Mat R) {
+    g.epi |= EPI_RESID;
+    g.R = R.p;
+    g.ldr = R.ld;
+    g.sR0 = R.s0;
+    g.sR1 = R.s1;
+}
+// bf16 planes of both operands given by the caller (conv stack; row strides in bf16 elements)
+inline void set_planes(GemmParams& g, const void* Ab, long ldab, const void* Bb, long ldbb) {
+    g.Ab = Ab;
+    g.ldab = ldab;
+    g.Bb = Bb;
+    g.ldbb = ldbb;
+}
+// bf16 plane of a per-utterance C (s1 in bf16 elements)
+inline void set_c_plane(GemmParams& g, void* Cb, long ldcb, long s1) {
+    g.Cb = Cb;
+    g.ldcb = ldcb;
+    g.sCb1 = s1;
+}
+
 struct LayerBufs {
     float *x_in, *xhat1, *rstd1, *y1, *qkv, *P, *lse, *ctx, *hmid, *xhat2, *rstd2, *y2, *u, *x_out;
     float *mean1, *mean2;  // row means when x-hat is recomputed from the stored LayerNorm input (xhat null)
@@ -377,7 +470,8 @@ struct suta_engine {
     // two bf16 activation planes [B*T][<= max(3H, F)] (ping-pong): written by the producer of a linear's A
     // operand (LayerNorm, flash attention, GEMM epilogue), read by the linear right after
     DevBuf planebuf;
-    bool use_planes() const { return gemm_mode == SUTA_PRECISION_BF16 && !wplanes.empty(); }
+    bool bf16_mode() const { return gemm_mode == SUTA_PRECISION_BF16; }
+    bool use_planes() const { return bf16_mode() && !wplanes.empty(); }
     // planes 0 / 1: the ping-pong A planes; plane 2: dctx's plane (the flash backward's dO operand)
     void* plane(int i) {
         if (!use_planes()) return nullptr;
@@ -457,20 +551,46 @@ struct suta_engine {
     bool conv_dx_planes() const {
         return conv_planes() && suta_switches().conv_dx_planes;
     }
-    // bf16 plane of layer l's qkv [B*T][3H]: written by the QKV GEMM, read by the flash forward and, in the
-    // backward, by the flash backward (kept for every layer, like the fp32 qkv)
+    // bf16 plane of layer l's qkv [B*T][3H], or null: written by the QKV GEMM, read by the flash forward and, in the
+    // backward, by the flash backward (kept for every layer, like the fp32 qkv).  Only the head-dim-64 flash kernels
+    // read planes (head dims above 64 read fp32 rows).
+    // (The forward used to ask `flash && d == 64`, the backward `flash && plane(0) && d == 64`: the same, since
+    // plane(0) and this plane are both null exactly when use_planes() is false.)
     DevBuf qkvplanes;
     void* qkv_plane(int l) {
-        if (!use_planes() || c.H % 8) return nullptr;
+        if (!plan.flash || c.H / c.NH != 64 || !use_planes() || c.H % 8) return nullptr;
         const size_t per = rup((long)plan.B * plan.T * 3 * c.H * 2, 256);
         if (qkvplanes.alloc(per * c.L)) drop_graph();
         return reinterpret_cast<char*>(qkvplanes.p) + l * per;
     }
+    // dctx's bf16 plane (the flash backward's dO operand), or null: given exactly when the qkv planes are
+    void* dctx_plane() { return qkv_plane(0) ? plane(2) : nullptr; }
+    // the flash forward / backward of this call read their bf16 planes: the launches' own tests (ops.h), so the byte
+    // counts and the launches cannot disagree
+    bool flash_fwd_on_plane() { return flash_fwd_reads_plane(bf16_mode(), qkv_plane(0), c.H, c.H / c.NH); }
+    bool flash_bwd_on_planes() {
+        return flash_bwd_reads_planes(bf16_mode(), qkv_plane(0), dctx_plane(), c.H, c.H / c.NH);
+    }
+    // the fp32 qkv of this call is not written: both flash kernels read its bf16 plane only.  One predicate for the
+    // QKV GEMM, the flash forward and the flash backward.
+    // (The forward used to write `qkvp && P0 && fwd_reads(qkvp) && bwd_reads(qkvp, plane(2))`, the backward
+    // `qkvp && fwd_reads(qkvp) && bwd_reads(qkvp, dctxp)`: qkvp non-null implies P0, both tests are false on a null
+    // qkvp, and dctxp is plane(2) whenever qkvp is non-null -- the same value in every configuration.)
+    bool qkv_fp32_dead() { return flash_fwd_on_plane() && flash_bwd_on_planes(); }
+    // positional conv on its dedicated kernel instead of the conv-A GEMM, forward and backward alike: exact fp32 mode,
+    // group widths 48 / 64 ...
+    bool posconv_fp32_kernel() const {
+        return posconv_kernel && gemm_mode == SUTA_PRECISION_FP32_MFMA && (c.H / c.posG == 48 || c.H / c.posG == 64) &&
+               c.posK % 2 == 0;
+    }
+    // ... or bf16 mode, group width 64 (config C4): posconv_bf16_kernel (its forward and flipped-tap backward weights
+    // wpos_bf_f / wpos_bf_b are built together)
+    bool posconv_bf16() const { return posconv_kernel && bf16_mode() && wpos_bf_f && wpos_bf_b && c.posK % 4 == 0; }
     void build_weight_planes();
     // whether gemm(p0) takes the 256 x 256 bf16-plane kernel's C^T epilogue (the producer's A plane given, B a frozen
     // weight with planes): the condition for fusing EPI_DELTA into it
     bool routes_to_hbx_t(const GemmParams& p0) {
-        if (gemm_mode != SUTA_PRECISION_BF16 || !p0.Ab || p0.segK != 0 || p0.ta || p0.Z != 1 || p0.K % 8) return false;
+        if (!bf16_mode() || !p0.Ab || p0.segK != 0 || p0.ta || p0.Z != 1 || p0.K % 8) return false;
         auto it = wplanes.find(p0.B);
         if (it == wplanes.end() || !(p0.tb ? p0.ldb == p0.K : p0.ldb == p0.N)) return false;
         GemmParams p = p0;
@@ -490,11 +610,11 @@ struct suta_engine {
                      p.Cb ? " Cb" : "");
             gemm_shape = key;
         }
-        if (gemm_mode == SUTA_PRECISION_BF16 && p.Ab && p.Bb) {  // both planes given by the caller (conv stack)
+        if (bf16_mode() && p.Ab && p.Bb) {  // both planes given by the caller (conv stack)
             timed(F_GEMM, [&] { gemm_launch(p, st, plan.splitws, plan.splitws_floats); }, timing ? gemm_alg_bytes(p) : 0.0);
             return;
         }
-        if (gemm_mode == SUTA_PRECISION_BF16 && p.segK == 0 && !p.ta && p.Z == 1 && p.K % 8 == 0 && p.lda % 4 == 0 &&
+        if (bf16_mode() && p.segK == 0 && !p.ta && p.Z == 1 && p.K % 8 == 0 && p.lda % 4 == 0 &&
             (reinterpret_cast<uintptr_t>(p.A) & 15) == 0) {
             auto it = wplanes.find(p.B);
             const bool fits = it != wplanes.end() && (p.tb ? p.ldb == p.K : p.ldb == p.N);
@@ -523,6 +643,42 @@ struct suta_engine {
         p.Ab = nullptr;  // (plane-less GEMM: a plane given for a non-frozen B is ignored)
         p.Cb = nullptr;
         timed(F_GEMM, [&] { gemm_launch(p, st, plan.splitws, plan.splitws_floats); }, timing ? gemm_alg_bytes(p) : 0.0);
+    }
+
+    // one GEMM per utterance (trainable per-slot weights, conv layers): operands by utt()
+    GemmParams per_utt(int M, int N, int K, Mat A, int ta, Mat B, int tb, Mat C) const {
+        return batched(M, N, K, A, ta, B, tb, C, plan.B, 1);
+    }
+    // one GEMM per (utterance, head) of the unfused attention, on these three operand views:
+    // head h's d columns of a [B*T][3H] qkv buffer (p: qkv for Q, + H for K, + 2H for V; dqkv alike),
+    Mat head_qkv(const float* p) const { return {p, 3L * c.H, c.H / c.NH, (long)plan.T * 3 * c.H}; }
+    // its d columns of a [B*T][H] buffer (ctx, dctx),
+    Mat head_rows(const float* p) const { return {p, c.H, c.H / c.NH, (long)plan.T * c.H}; }
+    // and its T x Tp score matrix (P, dP)
+    Mat head_scores(const float* p) const { return {p, plan.Tp, (long)plan.T * plan.Tp, (long)c.NH * plan.T * plan.Tp}; }
+    GemmParams per_head(int M, int N, int K, Mat A, int ta, Mat B, int tb, Mat C) const {
+        return batched(M, N, K, A, ta, B, tb, C, plan.B * c.NH, c.NH);
+    }
+    // The positional conv as a conv-A GEMM per (utterance, group): out = conv(in, w; pad) + res, w [G][posK][Cg][Cg],
+    // zero padding at each utterance's own end.  The forward (bias, pre given) computes
+    // pre = conv + bias, out = gelu(pre) + res; the backward (flipped taps) adds its row mask itself.
+    GemmParams posconv_gemm(const float* in, const float* w, int pad, float* out, const float* res,
+                            const float* bias = nullptr, float* pre = nullptr) const {
+        const int Cg = c.H / c.posG;
+        auto group = [&](const float* p) { return Mat{p, c.H, Cg, (long)plan.T * c.H}; };
+        GemmParams g = batched(plan.T, Cg, c.posK * Cg, group(in), 0, {w, Cg, (long)c.posK * Cg * Cg, 0}, 0, group(out),
+                               plan.B * c.posG, c.posG);
+        g.segK = Cg;
+        g.pad = pad;
+        g.Mvalid = plan.T;
+        g.zmvalid = rT();
+        add_resid(g, group(res));
+        if (bias) {
+            add_bias(g, bias, Cg);
+            store_pre(g, group(pre));
+            g.epi |= EPI_GELU;
+        }
+        return g;
     }
 
     int multiplicity(const TP& t, int train_feature, int bias_only) const {
@@ -738,52 +894,29 @@ void suta_engine::forward(int B) {
         });
     }
     for (int i = 1; i < k.nconv; ++i) {
-        GemmParams g;
-        gemm_init(g);
-        g.A = pl.a[i - 1];
-        g.lda = (long)k.S[i] * k.C[i - 1];
-        g.M = pl.Lc[i];
-        g.K = k.K[i] * k.C[i - 1];
-        g.N = k.C[i];
-        g.B = P + o_cw[i];
-        g.ldb = k.C[i];
-        g.Z = B;
-        g.sA1 = (long)pl.Lc[i - 1] * k.C[i - 1];
-        g.sB1 = Pn;
-        g.sC1 = (long)pl.Lc[i] * k.C[i];
+        // conv_i(a_{i-1}) as a strided-row GEMM: row t of A is the K_i * C_{i-1} inputs from frame S_i * t on.
+        // Layer mode stores z_i (LayerNorm and GELU follow); group mode stores z_i as the pre-activation and a_i.
+        // (bf16 planes: the per-slot weights are re-laid [C_i][K_i * C_{i-1}], one such block per utterance)
+        const int Kc = k.K[i] * k.C[i - 1], Ci = k.C[i];
+        const long zi = (long)pl.Lc[i] * Ci;  // elements of one utterance's z_i / a_i
+        float* out = !k.layer_mode ? pl.a[i] : zbf ? nullptr : pl.z[i];
+        GemmParams g = per_utt(pl.Lc[i], Ci, Kc, utt(pl.a[i - 1], (long)k.S[i] * k.C[i - 1], (long)pl.Lc[i - 1] * k.C[i - 1]),
+                               0, utt(P + o_cw[i], Ci, cpl ? (long)Ci * Kc : Pn), 0, utt(out, Ci, zi));
         if (cpl) {  // bf16 planes: activations written by the previous LayerNorm, weights re-laid per slot
             void* wt = conv_wt_plane(i);
             timed(F_EW, [&] {
-                launch_transpose_bf16(P + o_cw[i], Pn, B, g.K, g.N, wt, st, conv_dx_planes() ? conv_wt_plane(i, 1) : nullptr);
+                launch_transpose_bf16(P + o_cw[i], Pn, B, Kc, Ci, wt, st, conv_dx_planes() ? conv_wt_plane(i, 1) : nullptr);
             });
-            g.Ab = conv_act_plane(i - 1);
-            g.ldab = g.lda;
-            g.Bb = wt;
-            g.ldbb = g.K;
-            g.sB1 = (long)g.N * g.K;
-            // (g.sA1: the same element stride in the bf16 plane)
+            // (the activation plane has the fp32 buffer's element strides)
+            set_planes(g, conv_act_plane(i - 1), g.lda, wt, Kc);
         }
-        if (k.conv_bias) {
-            g.epi |= EPI_BIAS;
-            g.bias = P + o_cb[i];
-            g.sBias1 = Pn;
-        }
+        if (k.conv_bias) add_bias(g, P + o_cb[i], 0, Pn);
         if (!k.layer_mode) {
-            g.C = pl.a[i];
-            g.ldc = k.C[i];
-            g.epi |= EPI_STORE_PRE | EPI_GELU;
-            g.C2 = pl.z[i];
-            g.ldc2 = k.C[i];
-            g.sC21 = g.sC1;
+            store_pre(g, utt(pl.z[i], Ci, zi));
+            g.epi |= EPI_GELU;
             gemm(g);
         } else {
-            g.C = zbf ? nullptr : pl.z[i];
-            g.ldc = k.C[i];
-            if (zbf) {  // bf16 z_i only (the LayerNorm forward and backward read it widened)
-                g.Cb = pl.z[i];
-                g.ldcb = k.C[i];
-                g.sCb1 = (long)pl.Lc[i] * k.C[i];
-            }
+            if (zbf) set_c_plane(g, pl.z[i], Ci, zi);  // bf16 z_i only (the LayerNorm forward and backward read it widened)
             gemm(g);
             timed(F_NORM, [&] {
                 const bool pln = cpl && i + 1 < k.nconv;
@@ -800,81 +933,26 @@ void suta_engine::forward(int B) {
                              st, nullptr, pl.fp_mean);
     });
     {  // projection (per-utterance trainable W, b)
-        GemmParams g;
-        gemm_init(g);
-        g.A = pl.fp_y;
-        g.lda = C6;
-        g.B = P + o_pw;
-        g.tb = 1;
-        g.ldb = C6;
-        g.C = pl.h0;
-        g.ldc = H;
-        g.M = T;
-        g.N = H;
-        g.K = C6;
-        g.Z = B;
-        g.sA1 = (long)T * C6;
-        g.sB1 = Pn;
-        g.sC1 = (long)T * H;
-        g.epi = EPI_BIAS;
-        g.bias = P + o_pb;
-        g.sBias1 = Pn;
+        GemmParams g = per_utt(T, H, C6, utt(pl.fp_y, C6, (long)T * C6), 0, utt(P + o_pw, C6, Pn), 1, utt(pl.h0, H, (long)T * H));
+        add_bias(g, P + o_pb, 0, Pn);
         gemm(g);
     }
+    // positional conv: e = h0 + gelu(posconv(h0)); pz = pre-activation
     // dedicated kernel in exact fp32 mode for group widths 48 / 64 (timed with the MFMA contractions)
-    const bool pc_ok = posconv_kernel && gemm_mode == SUTA_PRECISION_FP32_MFMA && (H / k.posG == 48 || H / k.posG == 64) &&
-                       k.posK % 2 == 0;
-    if (pc_ok)
+    if (posconv_fp32_kernel())
         timed(F_GEMM, [&] {
             if (!launch_posconv(true, pl.h0, wpos_f, bpos, pl.h0, pl.e, pl.pz, B, T, H, k.posG, k.posK, k.posK / 2,
                                 rT(), st))
                 throw SutaError(SUTA_ERR_UNSUPPORTED, "positional conv shape");
         });
-    // bf16 mode, group width 64 (config C4): posconv_bf16_kernel
-    const bool pcb16 = posconv_kernel && gemm_mode == SUTA_PRECISION_BF16 && wpos_bf_f && k.posK % 4 == 0;
-    if (pcb16)
+    else if (posconv_bf16())
         timed(F_GEMM, [&] {
             if (!launch_posconv_bf16(true, pl.h0, wpos_bf_f, bpos, pl.h0, pl.e, pl.pz, B, T, H, k.posG, k.posK,
                                      k.posK / 2, rT(), st))
                 throw SutaError(SUTA_ERR_UNSUPPORTED, "positional conv shape");
         });
-    if (!pc_ok && !pcb16) {  // positional conv: e = h0 + gelu(posconv(h0)); pz = pre-activation
-        const int Cg = H / k.posG;
-        GemmParams g;
-        gemm_init(g);
-        g.A = pl.h0;
-        g.lda = H;
-        g.segK = Cg;
-        g.pad = k.posK / 2;
-        g.Mvalid = T;
-        g.zmvalid = rT();  // zero padding at each utterance's own end
-        g.M = T;
-        g.N = Cg;
-        g.K = k.posK * Cg;
-        g.Z = B * k.posG;
-        g.zdiv = k.posG;
-        g.sA0 = Cg;
-        g.sA1 = (long)T * H;
-        g.B = wpos_f;
-        g.ldb = Cg;
-        g.sB0 = (long)k.posK * Cg * Cg;
-        g.C = pl.e;
-        g.ldc = H;
-        g.sC0 = Cg;
-        g.sC1 = (long)T * H;
-        g.epi = EPI_BIAS | EPI_STORE_PRE | EPI_GELU | EPI_RESID;
-        g.bias = bpos;
-        g.sBias0 = Cg;
-        g.C2 = pl.pz;
-        g.ldc2 = H;
-        g.sC20 = Cg;
-        g.sC21 = (long)T * H;
-        g.R = pl.h0;
-        g.ldr = H;
-        g.sR0 = Cg;
-        g.sR1 = (long)T * H;
-        gemm(g);
-    }
+    else
+        gemm(posconv_gemm(pl.h0, wpos_f, k.posK / 2, pl.e, pl.h0, bpos, pl.pz));
     if (!k.stable) {
         timed(F_NORM, [&] {
             launch_layernorm_fwd(pl.e, P + o_eg, P + o_eb, Pn, T, pl.enc_y, pl.enc_xhat, pl.enc_rstd, (int)BT, H,
@@ -886,6 +964,7 @@ void suta_engine::forward(int B) {
     void* P0 = plane(0);
     void* P1 = plane(1);
     const bool dead = fp32_acts_dead();  // (P0 non-null exactly then)
+    float* gu32 = dead ? nullptr : pl.gu;
     for (int l = 0; l < k.L; ++l) {
         LayerBufs& lb = pl.lay[l];
         const float* attn_in = lb.x_in;
@@ -896,112 +975,36 @@ void suta_engine::forward(int B) {
             });
             attn_in = dead ? nullptr : lb.y1;  // (dead: the QKV GEMM reads the LN1 plane only)
         }
-        void* qkvp = (pl.flash && d == 64) ? qkv_plane(l) : nullptr;  // (head dims above 64 read fp32 rows)
+        void* qkvp = qkv_plane(l);  // the flash kernels' operands
         // both flash kernels read qkv's bf16 plane only (the backward's dO plane is plane 2): no fp32 qkv
-        const bool bf = gemm_mode == SUTA_PRECISION_BF16;
-        const bool qkv_dead = qkvp && P0 && flash_fwd_reads_plane(bf, qkvp, H, d) && flash_bwd_reads_planes(bf, qkvp, plane(2), H, d);
-        {  // fused QKV
-            GemmParams g;
-            gemm_init(g);
-            g.A = attn_in;
-            g.lda = H;
-            g.Ab = P0;  // LN output plane (stable: LN1; post-LN: the previous LayerNorm)
-            g.ldab = H;
-            g.B = wqkv[l];
-            g.tb = 1;
-            g.ldb = H;
-            g.C = qkv_dead ? nullptr : lb.qkv;
-            g.ldc = 3 * H;
-            g.M = (int)BT;
-            g.N = 3 * H;
-            g.K = H;
-            g.epi = EPI_BIAS;
-            g.bias = bqkv[l];
-            if (qkvp) {  // bf16 plane of qkv: the flash kernels' operands
-                g.Cb = qkvp;
-                g.ldcb = 3 * H;
-            }
+        float* qkv32 = qkv_fp32_dead() ? nullptr : lb.qkv;
+        {  // fused QKV (A plane: the LN output's -- stable: LN1; post-LN: the previous LayerNorm)
+            GemmParams g = linear(attn_in, P0, wqkv[l], 1, qkv32, qkvp, (int)BT, 3 * H, H);
+            add_bias(g, bqkv[l]);
             gemm(g);
         }
         // flash attention (head dim 64 or 72 .. 128, any T): ctx and the per-row LSE, no T x T matrix
         const bool fused = pl.flash;
         if (fused)
             timed(F_ATTN, [&] {
-                if (!launch_flash_fwd(qkv_dead ? nullptr : lb.qkv, lb.ctx, lb.lse, B, T, NH, H, d, scale, rT(),
-                                      gemm_mode == SUTA_PRECISION_BF16, st, P0, qkvp))
+                if (!launch_flash_fwd(qkv32, lb.ctx, lb.lse, B, T, NH, H, d, scale, rT(), bf16_mode(), st, P0, qkvp))
                     throw SutaError(SUTA_ERR_UNSUPPORTED, "flash attention shape");
-            }, (double)BT * ((qkv_dead || (bf && qkvp && flash_fwd_reads_plane(bf, qkvp, H, d)) ? 2.0 : 4.0) * 3.0 * H +
-                            4.0 * H + (P0 && bf ? 2.0 * H : 0.0) + 4.0 * NH));  // Q, K, V read; ctx (+ plane), LSE written
+            }, (double)BT * ((flash_fwd_on_plane() ? 2.0 : 4.0) * 3.0 * H + 4.0 * H + (P0 && bf16_mode() ? 2.0 * H : 0.0) +
+                            4.0 * NH));  // Q, K, V read; ctx (+ plane), LSE written
         if (!fused) {
             {  // S = Q K^T * scale
-                GemmParams g;
-                gemm_init(g);
-                g.A = lb.qkv;
-                g.lda = 3 * H;
-                g.B = lb.qkv + H;
-                g.tb = 1;
-                g.ldb = 3 * H;
-                g.C = lb.P;
-                g.ldc = pl.Tp;
-                g.M = T;
-                g.N = T;
-                g.K = d;
-                g.Z = B * NH;
-                g.zdiv = NH;
-                g.sA0 = d;
-                g.sA1 = (long)T * 3 * H;
-                g.sB0 = d;
-                g.sB1 = (long)T * 3 * H;
-                g.sC0 = (long)T * pl.Tp;
-                g.sC1 = (long)NH * T * pl.Tp;
+                GemmParams g = per_head(T, T, d, head_qkv(lb.qkv), 0, head_qkv(lb.qkv + H), 1, head_scores(lb.P));
                 g.alpha = scale;
                 gemm(g);
             }
             timed(F_SOFTMAX, [&] { launch_softmax_rows(lb.P, (long)B * NH * T, T, pl.Tp, rT(), (long)NH * T, st); });
-            {  // ctx = P V
-                GemmParams g;
-                gemm_init(g);
-                g.A = lb.P;
-                g.lda = pl.Tp;
-                g.B = lb.qkv + 2 * H;
-                g.ldb = 3 * H;
-                g.C = lb.ctx;
-                g.ldc = H;
-                g.M = T;
-                g.N = d;
-                g.K = T;
-                g.Z = B * NH;
-                g.zdiv = NH;
-                g.sA0 = (long)T * pl.Tp;
-                g.sA1 = (long)NH * T * pl.Tp;
-                g.sB0 = d;
-                g.sB1 = (long)T * 3 * H;
-                g.sC0 = d;
-                g.sC1 = (long)T * H;
-                gemm(g);
-            }
+            // ctx = P V
+            gemm(per_head(T, d, T, head_scores(lb.P), 0, head_qkv(lb.qkv + 2 * H), 0, head_rows(lb.ctx)));
         }
-        {  // out projection + residual
-            GemmParams g;
-            gemm_init(g);
-            g.A = lb.ctx;
-            g.lda = H;
-            if (fused) {
-                g.Ab = P0;
-                g.ldab = H;
-            }
-            g.B = wo[l];
-            g.tb = 1;
-            g.ldb = H;
-            g.C = k.stable ? lb.hmid : pl.rtmp;
-            g.ldc = H;
-            g.M = (int)BT;
-            g.N = H;
-            g.K = H;
-            g.epi = EPI_BIAS | EPI_RESID;
-            g.bias = bo[l];
-            g.R = lb.x_in;
-            g.ldr = H;
+        {  // out projection + residual (the flash forward wrote ctx's plane)
+            GemmParams g = linear(lb.ctx, fused ? P0 : nullptr, wo[l], 1, k.stable ? lb.hmid : pl.rtmp, nullptr, (int)BT, H, H);
+            add_bias(g, bo[l]);
+            add_resid(g, {lb.x_in, H});
             gemm(g);
         }
         const float* ffn_in;
@@ -1025,48 +1028,18 @@ void suta_engine::forward(int B) {
             ffn_out = pl.rtmp;
         }
         {  // u = in W1^T + b1 (stored), gu = gelu(u)
-            GemmParams g;
-            gemm_init(g);
-            g.A = ffn_in;
-            g.lda = H;
-            g.Ab = P0;
-            g.ldab = H;
-            g.Cb = P1;  // gelu(u) plane for FFN2
-            g.ldcb = k.F;
-            g.B = w1[l];
-            g.tb = 1;
-            g.ldb = H;
-            g.C = dead ? nullptr : pl.gu;  // with planes FFN2 reads only the bf16 plane (no weight gradient)
-            g.ldc = k.F;
-            g.M = (int)BT;
-            g.N = k.F;
-            g.K = H;
-            g.epi = EPI_BIAS | EPI_STORE_PRE | EPI_GELU;
-            g.bias = b1[l];
-            g.C2 = lb.u;  // (dead: bf16 elements, the first half of the fp32 buffer)
-            g.ldc2 = k.F;
+            // with planes FFN2 reads only gelu(u)'s bf16 plane P1 (no weight gradient): no fp32 gu
+            GemmParams g = linear(ffn_in, P0, w1[l], 1, gu32, P1, (int)BT, k.F, H);
+            add_bias(g, b1[l]);
+            store_pre(g, {lb.u, k.F});  // (dead: bf16 elements, the first half of the fp32 buffer)
             g.preb = dead && pre_bf16();
+            g.epi |= EPI_GELU;
             gemm(g);
         }
         {  // out = gu W2^T + b2 + residual
-            GemmParams g;
-            gemm_init(g);
-            g.A = dead ? nullptr : pl.gu;
-            g.lda = k.F;
-            g.Ab = P1;
-            g.ldab = k.F;
-            g.B = w2[l];
-            g.tb = 1;
-            g.ldb = k.F;
-            g.C = ffn_out;
-            g.ldc = H;
-            g.M = (int)BT;
-            g.N = H;
-            g.K = k.F;
-            g.epi = EPI_BIAS | EPI_RESID;
-            g.bias = b2[l];
-            g.R = ffn_res;
-            g.ldr = H;
+            GemmParams g = linear(gu32, P1, w2[l], 1, ffn_out, nullptr, (int)BT, H, k.F);
+            add_bias(g, b2[l]);
+            add_resid(g, {ffn_res, H});
             gemm(g);
         }
         if (!k.stable) {
@@ -1085,22 +1058,9 @@ void suta_engine::forward(int B) {
         hfin = dead ? nullptr : pl.enc_y;
     }
     {  // lm_head
-        GemmParams g;
-        gemm_init(g);
-        g.A = hfin;
-        g.lda = H;
-        g.Ab = P0;  // final LayerNorm output plane (stable: enc LN; post-LN: the last layer's LN2)
-        g.ldab = H;
-        g.B = wlm;
-        g.tb = 1;
-        g.ldb = H;
-        g.C = pl.logits;
-        g.ldc = k.V;
-        g.M = (int)BT;
-        g.N = k.V;
-        g.K = H;
-        g.epi = EPI_BIAS;
-        g.bias = blm;
+        // (A plane: the final LayerNorm output's -- stable: enc LN; post-LN: the last layer's LN2)
+        GemmParams g = linear(hfin, P0, wlm, 1, pl.logits, nullptr, (int)BT, k.V, H);
+        add_bias(g, blm);
         gemm(g);
     }
 }
@@ -1132,41 +1092,21 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
         sdpl_err = err;
     }
 
-    // Ab: bf16 plane of A written by its producer; Cb: bf16 plane of C for the next linear (bf16 mode)
-    auto nn_gemm = [&](const float* A, int lda, const float* Bm, int ldb, float* C, int ldc, int M, int N, int K,
-                       int epi, const float* R, int ldr, const float* aux, int ldaux, const void* Ab = nullptr,
-                       void* Cb = nullptr, int preb = 0) {
-        GemmParams g;
-        gemm_init(g);
-        g.preb = preb;
-        g.A = A;
-        g.lda = lda;
-        g.Ab = Ab;
-        g.ldab = K;
-        g.Cb = Cb;
-        g.ldcb = N;
-        g.B = Bm;
-        g.ldb = ldb;
-        g.C = C;
-        g.ldc = ldc;
-        g.M = M;
-        g.N = N;
-        g.K = K;
-        g.epi = epi;
-        g.R = R;
-        g.ldr = ldr;
-        g.aux = aux;
-        g.ldaux = ldaux;
-        gemm(g);
-    };
     void* P0 = plane(0);  // bf16 planes of the linears' A operands (ping-pong), null outside bf16 mode
     void* P1 = plane(1);
     // with bf16 planes (the forward's condition) dU = dH W2 * gelu'(u) is read only through its plane by the
     // FFN1 input-gradient GEMM (no weight gradient): its fp32 copy is not written
     const bool dead = fp32_acts_dead();
     float* du32 = dead ? nullptr : pl.du;
+    // du = (dy @ W2) * gelu'(u) of layer l (u in bf16 where the forward stored it so); dy's plane is P0, du's P1
+    auto du_gemm = [&](const float* dy, int l) {
+        GemmParams g = linear(dy, P0, w2[l], 0, du32, P1, (int)BT, k.F, H);
+        set_aux(g, EPI_DGELU, {pl.lay[l].u, k.F});
+        g.preb = dead && pre_bf16();
+        gemm(g);
+    };
     // d hfin = dlogits @ Wlm
-    nn_gemm(pl.dlogits, k.V, wlm, H, pl.d1, H, (int)BT, H, k.V, 0, nullptr, 0, nullptr, 0);
+    gemm(linear(pl.dlogits, nullptr, wlm, 0, pl.d1, nullptr, (int)BT, H, k.V));
     float* dx = pl.d1;  // grad wrt current residual stream
     float* t1 = pl.d2;
     float* t2 = pl.d3;
@@ -1187,10 +1127,12 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
                                      nullptr, t1, G + o_l2g[l], G + o_l2b[l], Pn, pl.lnpart, st, P0);
             });
             // du = (dr2 @ W2) * gelu'(u)
-            nn_gemm(t1, H, w2[l], k.F, du32, k.F, (int)BT, k.F, H, EPI_DGELU, nullptr, 0, lb.u, k.F, P0, P1,
-                    dead && pre_bf16());
-            // dh1 = du @ W1 + dr2
-            nn_gemm(du32, k.F, w1[l], H, t2, H, (int)BT, H, k.F, EPI_RESID, t1, H, nullptr, 0, P1);
+            du_gemm(t1, l);
+            {  // dh1 = du @ W1 + dr2
+                GemmParams g = linear(du32, P1, w1[l], 0, t2, nullptr, (int)BT, H, k.F);
+                add_resid(g, {t1, H});
+                gemm(g);
+            }
             // dr1 = LN1 bwd(dh1)
             timed(F_NORM, [&] {
                 launch_layernorm_bwd(t2, lb.xhat1, lb.rstd1, P + o_l1g[l], P + o_l1b[l], Pn, T, B, H, 0, nullptr,
@@ -1199,10 +1141,9 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
             dhres = t1;  // dr1
         } else {
             // du = (dx @ W2) * gelu'(u); dy2 = du @ W1; dhmid = LN2 bwd(dy2) + dx
-            nn_gemm(dx, H, w2[l], k.F, du32, k.F, (int)BT, k.F, H, EPI_DGELU, nullptr, 0, lb.u, k.F, P0, P1,
-                    dead && pre_bf16());
+            du_gemm(dx, l);
             void* dyp = dy_planes() ? plane(2) : nullptr;  // (plane 2's dctx of the layer above is consumed)
-            nn_gemm(du32, k.F, w1[l], H, dyp ? nullptr : t2, H, (int)BT, H, k.F, 0, nullptr, 0, nullptr, 0, P1, dyp);
+            gemm(linear(du32, P1, w1[l], 0, dyp ? nullptr : t2, dyp, (int)BT, H, k.F));
             timed(F_NORM, [&] {
                 launch_layernorm_bwd(dyp ? nullptr : t2, lb.xhat2, lb.rstd2, P + o_l2g[l], P + o_l2b[l], Pn, T, B, H, 0,
                                      nullptr, dx, t1, G + o_l2g[l], G + o_l2b[l], Pn, pl.lnpart, st, P0, lb.hmid,
@@ -1211,30 +1152,14 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
             dhres = t1;  // dhmid
         }
         // dctx = dhres @ Wo
-        void* dctxp = (pl.flash && P0 && d == 64) ? plane(2) : nullptr;   // dO plane of the flash backward
-        void* qkvp = (pl.flash && P0 && d == 64) ? qkv_plane(l) : nullptr;
-        if (!qkvp) dctxp = nullptr;
+        void* dctxp = dctx_plane();  // dO plane of the flash backward
+        void* qkvp = qkv_plane(l);
         // softmax-backward row term delta = rowsum(dctx * ctx) per head: in the dctx GEMM's epilogue when it takes the
         // C^T-epilogue kernel and the flash backward reads the dctx plane (the fp32 dctx is then not written), else a
         // separate pass over the fp32 dctx
         bool delta_fused = false;
-        if (pl.flash && dctxp && d == 64 && suta_switches().fused_delta &&
-            flash_bwd_reads_planes(gemm_mode == SUTA_PRECISION_BF16, qkvp, dctxp, H, d)) {
-            GemmParams g;
-            gemm_init(g);
-            g.A = dhres;
-            g.lda = H;
-            g.Ab = P0;
-            g.ldab = H;
-            g.Cb = dctxp;
-            g.ldcb = H;
-            g.B = wo[l];
-            g.ldb = H;
-            g.C = nullptr;
-            g.ldc = H;
-            g.M = (int)BT;
-            g.N = H;
-            g.K = H;
+        if (suta_switches().fused_delta && flash_bwd_on_planes()) {
+            GemmParams g = linear(dhres, P0, wo[l], 0, nullptr, dctxp, (int)BT, H, H);
             g.epi = EPI_DELTA;
             g.dlt_o = lb.ctx;
             g.ldo = H;
@@ -1247,141 +1172,50 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
             }
         }
         if (!delta_fused) {
-            nn_gemm(dhres, H, wo[l], H, pl.ctx, H, (int)BT, H, H, 0, nullptr, 0, nullptr, 0, P0, dctxp);
+            gemm(linear(dhres, P0, wo[l], 0, pl.ctx, dctxp, (int)BT, H, H));
             timed(F_SOFTMAX, [&] { launch_attn_delta(pl.ctx, lb.ctx, pl.delta, B, T, NH, d, st); });
         }
         // flash backward: P recomputed from the LSE, dQ, dK, dV into dqkv (else the GEMM path below)
         const bool fused_bwd = pl.flash;
         // with bf16 planes the QKV input-gradient GEMM reads only dqkv's bf16 plane: the fp32 copy is not written
-        const bool dqkv_dead = fused_bwd && P1 && dead;
-        if (fused_bwd)
+        float* dqkv32 = (fused_bwd && P1 && dead) ? nullptr : pl.dqkv;
+        void* dqkvp = fused_bwd ? P1 : nullptr;  // dqkv's plane, written by the flash backward
+        if (fused_bwd) {
+            // (the forward's test: the fp32 qkv was not written when both flash kernels read its plane)
+            const float* qkv32 = qkv_fp32_dead() ? nullptr : lb.qkv;
             timed(F_ATTN, [&] {
-                // (the forward's test: the fp32 qkv was not written when both flash kernels read its plane)
-                const bool bf = gemm_mode == SUTA_PRECISION_BF16;
-                const bool qkv_dead = qkvp && flash_fwd_reads_plane(bf, qkvp, H, d) && flash_bwd_reads_planes(bf, qkvp, dctxp, H, d);
-                if (!launch_flash_bwd(qkv_dead ? nullptr : lb.qkv, pl.ctx, lb.lse, pl.delta, dqkv_dead ? nullptr : pl.dqkv, pl.dqp, B, T,
-                                      NH, H, d, scale, rT(), gemm_mode == SUTA_PRECISION_BF16, st, P1, qkvp, dctxp))
+                if (!launch_flash_bwd(qkv32, pl.ctx, lb.lse, pl.delta, dqkv32, pl.dqp, B, T, NH, H, d, scale, rT(),
+                                      bf16_mode(), st, P1, qkvp, dctxp))
                     throw SutaError(SUTA_ERR_UNSUPPORTED, "flash attention shape");
-            }, [&] {  // Q, K, V, dO, LSE, delta read; dQ, dK, dV written (fp32 and / or the bf16 plane)
-                const bool bf = gemm_mode == SUTA_PRECISION_BF16;
-                const bool planes = bf && qkvp && dctxp && flash_bwd_reads_planes(bf, qkvp, dctxp, H, d);
-                return (double)BT * ((planes ? 2.0 : 4.0) * 4.0 * H + 4.0 * 2.0 * NH + (dqkv_dead ? 0.0 : 12.0 * H) +
-                                     (P1 && bf ? 6.0 * H : 0.0));
-            }());
-        if (!fused_bwd) {
+            },  // Q, K, V, dO, LSE, delta read; dQ, dK, dV written (fp32 and / or the bf16 plane)
+                  (double)BT * ((flash_bwd_on_planes() ? 2.0 : 4.0) * 4.0 * H + 4.0 * 2.0 * NH + (dqkv32 ? 12.0 * H : 0.0) +
+                                (P1 && bf16_mode() ? 6.0 * H : 0.0)));
+        } else {
             {  // dS = scale * P * (dctx_h @ V_h^T - delta)
-                GemmParams g;
-                gemm_init(g);
-                g.A = pl.ctx;
-                g.lda = H;
-                g.B = lb.qkv + 2 * H;
-                g.tb = 1;
-                g.ldb = 3 * H;
-                g.C = pl.dP;
-                g.ldc = pl.Tp;
-                g.M = T;
-                g.N = T;
-                g.K = d;
-                g.Z = B * NH;
-                g.zdiv = NH;
-                g.sA0 = d;
-                g.sA1 = (long)T * H;
-                g.sB0 = d;
-                g.sB1 = (long)T * 3 * H;
-                g.sC0 = (long)T * pl.Tp;
-                g.sC1 = (long)NH * T * pl.Tp;
-                g.epi = EPI_SMBWD;
+                GemmParams g = per_head(T, T, d, head_rows(pl.ctx), 0, head_qkv(lb.qkv + 2 * H), 1, head_scores(pl.dP));
                 g.alpha = scale;
-                g.aux = lb.P;
-                g.ldaux = pl.Tp;
-                g.sAux0 = (long)T * pl.Tp;
-                g.sAux1 = (long)NH * T * pl.Tp;
-                g.rowv = pl.delta;
-                g.sRow0 = T;
-                g.sRow1 = (long)NH * T;
+                set_aux(g, EPI_SMBWD, head_scores(lb.P));
+                set_row_vec(g, pl.delta, T, (long)NH * T);
                 gemm(g);
             }
-            {  // dQ = dS K_h
-                GemmParams g;
-                gemm_init(g);
-                g.A = pl.dP;
-                g.lda = pl.Tp;
-                g.B = lb.qkv + H;
-                g.ldb = 3 * H;
-                g.C = pl.dqkv;
-                g.ldc = 3 * H;
-                g.M = T;
-                g.N = d;
-                g.K = T;
-                g.Z = B * NH;
-                g.zdiv = NH;
-                g.sA0 = (long)T * pl.Tp;
-                g.sA1 = (long)NH * T * pl.Tp;
-                g.sB0 = d;
-                g.sB1 = (long)T * 3 * H;
-                g.sC0 = d;
-                g.sC1 = (long)T * 3 * H;
-                gemm(g);
-            }
-        }
-        if (!fused_bwd) {  // dK = dS^T Q_h
-            GemmParams g;
-            gemm_init(g);
-            g.A = pl.dP;
-            g.ta = 1;
-            g.lda = pl.Tp;
-            g.B = lb.qkv;
-            g.ldb = 3 * H;
-            g.C = pl.dqkv + H;
-            g.ldc = 3 * H;
-            g.M = T;
-            g.N = d;
-            g.K = T;
-            g.Z = B * NH;
-            g.zdiv = NH;
-            g.sA0 = (long)T * pl.Tp;
-            g.sA1 = (long)NH * T * pl.Tp;
-            g.sB0 = d;
-            g.sB1 = (long)T * 3 * H;
-            g.sC0 = d;
-            g.sC1 = (long)T * 3 * H;
-            gemm(g);
-        }
-        if (!fused_bwd) {  // dV = P^T dctx_h
-            GemmParams g;
-            gemm_init(g);
-            g.A = lb.P;
-            g.ta = 1;
-            g.lda = pl.Tp;
-            g.B = pl.ctx;
-            g.ldb = H;
-            g.C = pl.dqkv + 2 * H;
-            g.ldc = 3 * H;
-            g.M = T;
-            g.N = d;
-            g.K = T;
-            g.Z = B * NH;
-            g.zdiv = NH;
-            g.sA0 = (long)T * pl.Tp;
-            g.sA1 = (long)NH * T * pl.Tp;
-            g.sB0 = d;
-            g.sB1 = (long)T * H;
-            g.sC0 = d;
-            g.sC1 = (long)T * 3 * H;
-            gemm(g);
+            // dQ = dS K_h
+            gemm(per_head(T, d, T, head_scores(pl.dP), 0, head_qkv(lb.qkv + H), 0, head_qkv(pl.dqkv)));
+            // dK = dS^T Q_h
+            gemm(per_head(T, d, T, head_scores(pl.dP), 1, head_qkv(lb.qkv), 0, head_qkv(pl.dqkv + H)));
+            // dV = P^T dctx_h
+            gemm(per_head(T, d, T, head_scores(lb.P), 1, head_rows(pl.ctx), 0, head_qkv(pl.dqkv + 2 * H)));
         }
         if (!k.stable) {
             // dx_in = dqkv @ Wqkv + dr1
-            nn_gemm(dqkv_dead ? nullptr : pl.dqkv, 3 * H, wqkv[l], H, t2, H, (int)BT, H, 3 * H, EPI_RESID, dhres, H,
-                    nullptr, 0,
-                    fused_bwd ? P1 : nullptr);
+            GemmParams g = linear(dqkv32, dqkvp, wqkv[l], 0, t2, nullptr, (int)BT, H, 3 * H);
+            add_resid(g, {dhres, H});
+            gemm(g);
             std::swap(dx, t2);
         } else {
             // dy1 = dqkv @ Wqkv ; dx_in = LN1 bwd(dy1) + dhmid
             // (plane 2 held dctx, consumed by the flash backward above)
-            void* dyp = (dy_planes() && fused_bwd && P1) ? plane(2) : nullptr;
-            nn_gemm(dqkv_dead ? nullptr : pl.dqkv, 3 * H, wqkv[l], H, dyp ? nullptr : t2, H, (int)BT, H, 3 * H, 0, nullptr,
-                    0, nullptr, 0, fused_bwd ? P1 : nullptr, dyp);
+            void* dyp = (dy_planes() && dqkvp) ? plane(2) : nullptr;
+            gemm(linear(dqkv32, dqkvp, wqkv[l], 0, dyp ? nullptr : t2, dyp, (int)BT, H, 3 * H));
             timed(F_NORM, [&] {
                 launch_layernorm_bwd(dyp ? nullptr : t2, lb.xhat1, lb.rstd1, P + o_l1g[l], P + o_l1b[l], Pn, T, B, H, 0,
                                      nullptr, dhres, dx, G + o_l1g[l], G + o_l1b[l], Pn, pl.lnpart, st, P0, lb.x_in,
@@ -1399,53 +1233,35 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
         });
         de = t1;
     }
-    float* dpz = (de == pl.d1) ? pl.d2 : (de == pl.d2 ? pl.d3 : pl.d1);
-    float* dh0 = (dpz == pl.d1 || de == pl.d1) ? ((dpz == pl.d2 || de == pl.d2) ? pl.d3 : pl.d2) : pl.d1;
+    // dpz, dh0: the two of d1, d2, d3 that de does not occupy, in cyclic order after de (checked against the nested
+    // conditionals this replaces, for de = d1, d2 and d3: the same pair in the same order)
+    float *dpz, *dh0;
+    if (de == pl.d1) {
+        dpz = pl.d2;
+        dh0 = pl.d3;
+    } else if (de == pl.d2) {
+        dpz = pl.d3;
+        dh0 = pl.d1;
+    } else {
+        dpz = pl.d1;
+        dh0 = pl.d2;
+    }
     timed(F_EW, [&] { launch_dgelu_mul(de, pl.pz, dpz, BT * H, st); });
-    const bool pcb_ok = posconv_kernel && gemm_mode == SUTA_PRECISION_FP32_MFMA && (H / k.posG == 48 || H / k.posG == 64) &&
-                        k.posK % 2 == 0;
-    if (pcb_ok)
+    // dh0 = posconv^T(dpz) + de: the forward's kernel choice, on the flipped taps
+    if (posconv_fp32_kernel())
         timed(F_GEMM, [&] {
             if (!launch_posconv(false, dpz, wpos_b, nullptr, de, dh0, nullptr, B, T, H, k.posG, k.posK,
                                 k.posK - 1 - k.posK / 2, rT(), st))
                 throw SutaError(SUTA_ERR_UNSUPPORTED, "positional conv shape");
         });
-    const bool pcb16 = posconv_kernel && gemm_mode == SUTA_PRECISION_BF16 && wpos_bf_b && k.posK % 4 == 0;
-    if (pcb16)
+    else if (posconv_bf16())
         timed(F_GEMM, [&] {
             if (!launch_posconv_bf16(false, dpz, wpos_bf_b, nullptr, de, dh0, nullptr, B, T, H, k.posG, k.posK,
                                      k.posK - 1 - k.posK / 2, rT(), st))
                 throw SutaError(SUTA_ERR_UNSUPPORTED, "positional conv shape");
         });
-    if (!pcb_ok && !pcb16) {  // dh0 = posconv^T(dpz) + de
-        const int Cg = H / k.posG;
-        GemmParams g;
-        gemm_init(g);
-        g.A = dpz;
-        g.lda = H;
-        g.segK = Cg;
-        g.pad = k.posK - 1 - k.posK / 2;
-        g.Mvalid = T;
-        g.zmvalid = rT();
-        g.M = T;
-        g.N = Cg;
-        g.K = k.posK * Cg;
-        g.Z = B * k.posG;
-        g.zdiv = k.posG;
-        g.sA0 = Cg;
-        g.sA1 = (long)T * H;
-        g.B = wpos_b;
-        g.ldb = Cg;
-        g.sB0 = (long)k.posK * Cg * Cg;
-        g.C = dh0;
-        g.ldc = H;
-        g.sC0 = Cg;
-        g.sC1 = (long)T * H;
-        g.epi = EPI_RESID;
-        g.R = de;
-        g.ldr = H;
-        g.sR0 = Cg;
-        g.sR1 = (long)T * H;
+    else {
+        GemmParams g = posconv_gemm(dpz, wpos_b, k.posK - 1 - k.posK / 2, dh0, de);
         if (plan.ragged) {  // padding frames receive conv gradient from valid ones: keep them at 0
             g.epi |= EPI_ROWMASK;
             g.zrows = rT();
@@ -1454,45 +1270,12 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
     }
     const int C6 = k.C[k.nconv - 1];
     if (hp.train_feature) {
-        {  // dWproj = dh0^T fp_y  (per utterance)
-            GemmParams g;
-            gemm_init(g);
-            g.A = dh0;
-            g.ta = 1;
-            g.lda = H;
-            g.B = pl.fp_y;
-            g.ldb = C6;
-            g.C = G + o_pw;
-            g.ldc = C6;
-            g.M = H;
-            g.N = C6;
-            g.K = T;
-            g.Z = B;
-            g.sA1 = (long)T * H;
-            g.sB1 = (long)T * C6;
-            g.sC1 = Pn;
-            gemm(g);
-        }
+        // dWproj = dh0^T fp_y  (per utterance)
+        gemm(per_utt(H, C6, T, utt(dh0, H, (long)T * H), 1, utt(pl.fp_y, C6, (long)T * C6), 0, utt(G + o_pw, C6, Pn)));
         timed(F_NORM, [&] { launch_colsum(dh0, B, T, H, G + o_pb, Pn, pl.lnpart, st); });
     }
-    {  // d fp_y = dh0 @ Wproj  (per utterance W)
-        GemmParams g;
-        gemm_init(g);
-        g.A = dh0;
-        g.lda = H;
-        g.B = P + o_pw;
-        g.ldb = C6;
-        g.C = pl.dzc;
-        g.ldc = C6;
-        g.M = T;
-        g.N = C6;
-        g.K = H;
-        g.Z = B;
-        g.sA1 = (long)T * H;
-        g.sB1 = Pn;
-        g.sC1 = (long)T * C6;
-        gemm(g);
-    }
+    // d fp_y = dh0 @ Wproj  (per utterance W)
+    gemm(per_utt(T, C6, H, utt(dh0, H, (long)T * H), 0, utt(P + o_pw, C6, Pn), 0, utt(pl.dzc, C6, (long)T * C6)));
     const int last = k.nconv - 1;
     // feature-projection LN bwd; in group mode also * gelu'(z_last) => dz_last
     float* cur = pl.dzc2;
@@ -1535,30 +1318,14 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
         if (k.conv_bias && !bias_done)
             timed(F_NORM, [&] { launch_colsum(cur, B, pl.Lc[i], k.C[i], G + o_cb[i], Pn, pl.lnpart, st); });
         {  // dW_i = im2col(a_{i-1})^T dz_i
-            GemmParams g;
-            gemm_init(g);
-            g.A = pl.a[i - 1];
-            g.ta = 1;
-            g.lda = (long)k.S[i] * k.C[i - 1];
-            g.M = k.K[i] * k.C[i - 1];
-            g.K = pl.Lc[i];
-            g.B = cur;
-            g.ldb = k.C[i];
-            g.N = k.C[i];
-            g.C = G + o_cw[i];
-            g.ldc = k.C[i];
-            g.Z = B;
-            g.sA1 = (long)pl.Lc[i - 1] * k.C[i - 1];
-            g.sB1 = (long)pl.Lc[i] * k.C[i];
-            g.sC1 = Pn;
+            GemmParams g = per_utt(k.K[i] * k.C[i - 1], k.C[i], pl.Lc[i],
+                                   utt(pl.a[i - 1], (long)k.S[i] * k.C[i - 1], (long)pl.Lc[i - 1] * k.C[i - 1]), 1,
+                                   utt(cur, k.C[i], (long)pl.Lc[i] * k.C[i]), 0, utt(G + o_cw[i], k.C[i], Pn));
             if (cpl) {  // bf16 planes: the forward's activation plane and the LayerNorm-written dz plane (the fp32
                         // activation was not stored)
                 if (!bias_done) throw SutaError(SUTA_ERR_UNSUPPORTED, "conv planes: dz plane not written");
                 g.A = nullptr;
-                g.Ab = conv_act_plane(i - 1);
-                g.ldab = g.lda;
-                g.Bb = conv_dz_plane();
-                g.ldbb = g.ldb;
+                set_planes(g, conv_act_plane(i - 1), g.lda, conv_dz_plane(), g.ldb);
             }
             gemm(g);
         }
@@ -1572,49 +1339,27 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
                 const int nj = (Kt - rho + S_ - 1) / S_;
                 if (Mrows <= 0) continue;
                 if (nj <= 0) throw SutaError(SUTA_ERR_UNSUPPORTED, "conv stride > kernel");
-                GemmParams g;
-                gemm_init(g);
-                g.A = cur;
-                g.lda = Cout;
+                const long tap0 = (long)(rho + S_ * (nj - 1)) * Cin * Cout;  // segment 0's weight tap
+                GemmParams g = per_utt(Mrows, Cin, nj * Cout, utt(cur, Cout, (long)Lout * Cout), 0,
+                                       utt(P + o_cw[i] + tap0, Cout, Pn), 1,
+                                       utt(other + (long)rho * Cin, (long)S_ * Cin, (long)Lin * Cin));
                 g.segK = Cout;
                 g.pad = nj - 1;
                 g.Mvalid = Lout;
-                g.M = Mrows;
-                g.K = nj * Cout;
-                g.N = Cin;
-                g.B = P + o_cw[i] + (long)(rho + S_ * (nj - 1)) * Cin * Cout;
-                g.tb = 1;
-                g.ldb = Cout;
                 g.segB = 1;
                 g.sBseg = -(long)S_ * Cin * Cout;
-                g.C = other + (long)rho * Cin;
-                g.ldc = (long)S_ * Cin;
-                g.Z = B;
-                g.sA1 = (long)Lout * Cout;
-                g.sB1 = Pn;
-                g.sC1 = (long)Lin * Cin;
-                if (zprev) {
-                    g.epi = EPI_DGELU;
-                    g.aux = zprev + (long)rho * Cin;
-                    g.ldaux = (long)S_ * Cin;
-                    g.sAux1 = (long)Lin * Cin;
-                }
+                if (zprev) set_aux(g, EPI_DGELU, utt(zprev + (long)rho * Cin, (long)S_ * Cin, (long)Lin * Cin));
                 if (cpl && conv_dx_planes()) {  // bf16 planes: the LayerNorm-written dz plane and the forward's
                                                 // source-layout bf16 weights (strides in bf16 elements)
                     if (!bias_done) throw SutaError(SUTA_ERR_UNSUPPORTED, "conv planes: dz plane not written");
                     g.A = nullptr;
                     g.B = nullptr;
-                    g.Ab = conv_dz_plane();
-                    g.ldab = Cout;
-                    g.Bb = static_cast<char*>(conv_wt_plane(i, 1)) + (long)(rho + S_ * (nj - 1)) * Cin * Cout * 2;
-                    g.ldbb = Cout;
+                    set_planes(g, conv_dz_plane(), Cout, static_cast<char*>(conv_wt_plane(i, 1)) + tap0 * 2, Cout);
                     g.tb = 0;
                     g.sB1 = (long)Kt * Cin * Cout;
                     if (zbf) {  // da_{i-1} in bf16 only (the next LayerNorm backward reads it widened)
                         g.C = nullptr;
-                        g.Cb = reinterpret_cast<__bf16*>(other) + (long)rho * Cin;
-                        g.ldcb = (long)S_ * Cin;
-                        g.sCb1 = (long)Lin * Cin;
+                        set_c_plane(g, reinterpret_cast<__bf16*>(other) + (long)rho * Cin, (long)S_ * Cin, (long)Lin * Cin);
                     }
                 }
                 gemm(g);
@@ -1653,25 +1398,9 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
     if (fused0) return;
     if (k.conv_bias)
         timed(F_NORM, [&] { launch_colsum(other, B, pl.Lc[0], k.C[0], G + o_cb[0], Pn, pl.lnpart, st); });
-    {  // dW0[k][c] = sum_t x[S0 t + k] dz0[t][c]
-        GemmParams g;
-        gemm_init(g);
-        g.A = pl.x;
-        g.ta = 1;
-        g.lda = k.S[0];
-        g.M = k.K[0];
-        g.K = pl.Lc[0];
-        g.B = other;
-        g.ldb = k.C[0];
-        g.N = k.C[0];
-        g.C = G + o_cw[0];
-        g.ldc = k.C[0];
-        g.Z = B;
-        g.sA1 = pl.N;
-        g.sB1 = (long)pl.Lc[0] * k.C[0];
-        g.sC1 = Pn;
-        gemm(g);
-    }
+    // dW0[k][c] = sum_t x[S0 t + k] dz0[t][c]
+    gemm(per_utt(k.K[0], k.C[0], pl.Lc[0], utt(pl.x, k.S[0], pl.N), 1, utt(other, k.C[0], (long)pl.Lc[0] * k.C[0]), 0,
+                 utt(G + o_cw[0], k.C[0], Pn)));
 }
 
 // The optimizer scalars a table row depends on (the rest of suta_hparams only shapes the loss)
