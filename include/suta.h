@@ -69,6 +69,7 @@ typedef struct suta_model_config {
     int32_t num_conv_pos_embeddings;       /* 128 */
     int32_t num_conv_pos_embedding_groups; /* 16 */
     float layer_norm_eps;                  /* 1e-5 */
+    int32_t adapter_attn_dim;              /* 0 = none; MMS: 16 */
 } suta_model_config;
 
 /* forward_and_adapt / setup_optimizer / collect_params arguments (main.py:8-23, 62-103, 172-173)
@@ -107,7 +108,16 @@ typedef struct suta_hparams {
  * max_samples: longest utterance any later call may pass (the reference truncates to 600000,
  * data.py); longer inputs return SUTA_ERR_ARG; <= 0 means no limit beyond T <= 2048 frames.
  * cfg->vocab_size: 1 .. 1024 (any Wav2Vec2ForCTC head: letters, XLSR fine-tunes, phoneme sets); larger
- * returns SUTA_ERR_UNSUPPORTED.  Class 0 is the CTC blank of the non-blank mask, as the reference
+ * returns SUTA_ERR_UNSUPPORTED.
+ * cfg->adapter_attn_dim = A > 0 with do_stable_layer_norm: every encoder layer ends in HF's Wav2Vec2AttnAdapterLayer
+ * (MMS: facebook/mms-1b-all and its kin), h = h + linear_2(relu(linear_1(norm(h)))), and the six tensors
+ * "wav2vec2.encoder.layers.N.adapter_layer.{norm,linear_1,linear_2}.{weight,bias}" are required (a missing one
+ * returns SUTA_ERR_ARG naming it).  norm is an nn.LayerNorm (eps 1e-5 whatever layer_norm_eps says), so its weight and
+ * bias are trainables like every other LayerNorm's (suta_get_param, suta_param_info; multiplicity 1, bias only under
+ * bias_only).  1 <= A <= 64; larger returns SUTA_ERR_UNSUPPORTED.  With do_stable_layer_norm == 0 the field is
+ * ignored, as HF's post-LN layer builds no adapter: the tensors are neither required nor read.  Both adapter kernels
+ * count into timing family 2 (norm).
+ * Class 0 is the CTC blank of the non-blank mask, as the reference
  * hard-codes it (main.py:178-184).  The SDPL objective (pl_coef > 0) runs at every vocab_size once
  * suta_set_pseudo_labels has given it the checkpoint's own vocabulary; without a table it builds its pseudo labels
  * by the 32-letter rule of facebook/wav2vec2-base-960h, which names a vocabulary only up to 32 classes: above that
@@ -254,7 +264,11 @@ int32_t suta_get_census(char* buf, int64_t cap, int64_t* needed);
  *                                   accumulation; activations, norms, softmax, loss, AdamW and the
  *                                   trainable master tensors stay fp32 (torch.autocast(bf16)
  *                                   semantics for the matmuls) -- tests/parity.py (assert_bf16_close) states the
- *                                   tolerance, tests/test_gpu_large_bf16.py applies it */
+ *                                   tolerance, tests/test_gpu_large_bf16.py applies it.
+ *                                   Stated deviation from autocast: the attention adapter (adapter_attn_dim) is
+ *                                   exact fp32 in all three modes.  Its input, the residual stream, is fp32 in bf16
+ *                                   mode too, and the kernel is HBM-bound (8 FLOP per byte at A = 16), so bf16
+ *                                   operands would buy no time. */
 #define SUTA_PRECISION_FP32_MFMA 0
 #define SUTA_PRECISION_FP32_SPLIT_BF16 1
 #define SUTA_PRECISION_BF16 2

@@ -25,6 +25,11 @@ _LARGE = dict(_BASE, hidden_size=1024, num_hidden_layers=24, num_attention_heads
 # groups of width 80 / 120.  vocab_size is the fine-tune's; a checkpoint directory's config.json governs.
 _XLSR_1B = dict(_LARGE, hidden_size=1280, num_hidden_layers=48, num_attention_heads=16, intermediate_size=5120)
 _XLSR_2B = dict(_LARGE, hidden_size=1920, num_hidden_layers=48, num_attention_heads=16, intermediate_size=7680)
+# MMS (facebook/mms-1b-all, -fl102, -l1107): the XLS-R 1B body plus one attention adapter per encoder layer
+# (`adapter_attn_dim`, HF Wav2Vec2AttnAdapterLayer) and one adapter file per language (main.py --target_lang).
+# vocab_size 154 is quoted from memory and could not be verified offline; a checkpoint directory's config.json
+# governs, and --target_lang takes the size of the language's own lm_head.
+_MMS_1B = dict(_XLSR_1B, adapter_attn_dim=16, vocab_size=154)
 
 # Tiny geometries used for the committed golden vectors (tests/golden/make_golden.py).
 _TINY_GROUP = dict(_BASE, hidden_size=64, num_hidden_layers=2, num_attention_heads=4, intermediate_size=128,
@@ -34,6 +39,9 @@ _TINY_LAYER = dict(_TINY_GROUP, conv_bias=True, feat_extract_norm="layer", do_st
 _TINY_HD80 = dict(_TINY_LAYER, hidden_size=160, num_attention_heads=2, num_conv_pos_embedding_groups=2,
                   intermediate_size=320)
 _TINY_HD120 = dict(_TINY_HD80, hidden_size=240)
+# attention adapters at test size: the MMS width 16, and a width that is no multiple of the kernels' 16-column tile
+_TINY_LAYER_A16 = dict(_TINY_LAYER, adapter_attn_dim=16)
+_TINY_HD80_A5 = dict(_TINY_HD80, adapter_attn_dim=5)
 
 PRESETS = {
     "facebook/wav2vec2-base-960h": _BASE,
@@ -45,11 +53,22 @@ PRESETS = {
     "wav2vec2-xls-r-1b": _XLSR_1B,
     "facebook/wav2vec2-xls-r-2b": _XLSR_2B,
     "wav2vec2-xls-r-2b": _XLSR_2B,
+    "facebook/mms-1b-all": _MMS_1B,
+    "mms-1b-all": _MMS_1B,
     "tiny-group": _TINY_GROUP,
     "tiny-layer": _TINY_LAYER,
     "tiny-hd80": _TINY_HD80,
     "tiny-hd120": _TINY_HD120,
+    "tiny-layer-a16": _TINY_LAYER_A16,
+    "tiny-hd80-a5": _TINY_HD80_A5,
 }
+
+
+def adapter_dim(cfg: dict) -> int:
+    """Width A of the per-layer attention adapter (HF `adapter_attn_dim`), 0 for none.  HF builds the adapter only in
+    the stable-LN encoder layer (`Wav2Vec2EncoderLayerStableLayerNorm`); the post-LN layer class ignores the field."""
+    a = cfg.get("adapter_attn_dim")
+    return int(a) if a and cfg["do_stable_layer_norm"] else 0
 
 
 def head_dim(cfg: dict) -> int:
@@ -75,6 +94,8 @@ def get_config(name_or_path: str) -> dict:
         for k in cfg:
             if k in raw:
                 cfg[k] = raw[k]
+        if raw.get("adapter_attn_dim") is not None:   # MMS; absent or null: no adapters (the key stays out)
+            cfg["adapter_attn_dim"] = int(raw["adapter_attn_dim"])
         return cfg
     raise KeyError(f"unknown model '{name_or_path}': not a preset and no config.json found")
 
@@ -114,6 +135,7 @@ def param_shapes(cfg: dict):
             (pc + "parametrizations.weight.original1", (H, H // G, K))]
     out += [("wav2vec2.encoder.layer_norm.weight", (H,)), ("wav2vec2.encoder.layer_norm.bias", (H,))]
     F_ = cfg["intermediate_size"]
+    A = adapter_dim(cfg)
     for li in range(cfg["num_hidden_layers"]):
         lp = f"wav2vec2.encoder.layers.{li}."
         for pr in ("k_proj", "v_proj", "q_proj", "out_proj"):
@@ -124,5 +146,10 @@ def param_shapes(cfg: dict):
                 (lp + "feed_forward.output_dense.weight", (H, F_)),
                 (lp + "feed_forward.output_dense.bias", (H,)),
                 (lp + "final_layer_norm.weight", (H,)), (lp + "final_layer_norm.bias", (H,))]
+        if A:
+            ap = lp + "adapter_layer."
+            out += [(ap + "norm.weight", (H,)), (ap + "norm.bias", (H,)),
+                    (ap + "linear_1.weight", (A, H)), (ap + "linear_1.bias", (A,)),
+                    (ap + "linear_2.weight", (H, A)), (ap + "linear_2.bias", (H,))]
     out += [("lm_head.weight", (cfg["vocab_size"], H)), ("lm_head.bias", (cfg["vocab_size"],))]
     return out

@@ -62,6 +62,7 @@ struct Cfg {
     int H, L, NH, F, V, nconv;
     int C[SUTA_MAX_CONV], K[SUTA_MAX_CONV], S[SUTA_MAX_CONV];
     int conv_bias, layer_mode, stable, posK, posG;
+    int A;  // attention-adapter width of the stable-LN layers (MMS: 16); 0 = none
     float eps;
 };
 
@@ -254,6 +255,8 @@ inline void set_c_plane(GemmParams& g, void* Cb, long ldcb, long s1) {
 struct LayerBufs {
     float *x_in, *xhat1, *rstd1, *y1, *qkv, *P, *lse, *ctx, *hmid, *xhat2, *rstd2, *y2, *u, *x_out;
     float *mean1, *mean2;  // row means when x-hat is recomputed from the stored LayerNorm input (xhat null)
+    // attention adapter (A > 0): its input (the FFN output; the adapter kernel writes x_out) and LayerNorm row statistics
+    float *ad_in, *ad_mean, *ad_rstd;
 };
 
 struct Plan {
@@ -301,6 +304,7 @@ struct suta_engine {
     bool bf16_planes = true;     // bf16 mode: linears on bf16 operand planes; env SUTA_BF16_PLANES=0 off
     // frozen weights
     std::vector<float*> wqkv, bqkv, wo, bo, w1, b1, w2, b2;
+    std::vector<AdapterW> adw;  // attention adapters' frozen linears, zero-padded in both orientations (ops.h)
     float *wpos_f = nullptr, *wpos_b = nullptr, *bpos = nullptr, *wlm = nullptr, *blm = nullptr;
     // bf16 positional-conv weights [G][K][n][k] (fwd: n = c_out, k = c_in; bwd: taps flipped, n = c_in, k = c_out)
     // for posconv_bf16_kernel (group width 64); null otherwise
@@ -314,7 +318,7 @@ struct suta_engine {
     // offsets of trainable pieces
     long o_cw[SUTA_MAX_CONV], o_cb[SUTA_MAX_CONV], o_cg[SUTA_MAX_CONV], o_cbeta[SUTA_MAX_CONV];
     long o_fpg, o_fpb, o_pw, o_pb, o_eg, o_eb;
-    std::vector<long> o_l1g, o_l1b, o_l2g, o_l2b;
+    std::vector<long> o_l1g, o_l1b, o_l2g, o_l2b, o_adg, o_adb;
     // workspace
     DevBuf ws;
     Plan plan;
@@ -789,6 +793,10 @@ void suta_engine::build_plan(int B, long N) {
             lb.y2 = k.stable ? ar.take<float>(BT * H) : nullptr;
             lb.u = ar.take<float>(BT * k.F);
             lb.x_out = ar.take<float>(BT * H);
+            const bool ad = k.stable && k.A > 0;
+            lb.ad_in = ad ? ar.take<float>(BT * H) : nullptr;
+            lb.ad_mean = ad ? ar.take<float>(BT) : nullptr;
+            lb.ad_rstd = ad ? ar.take<float>(BT) : nullptr;
         }
         for (int l = 0; l < k.L; ++l) {
             pl.lay[l].x_in = l == 0 ? (k.stable ? pl.e : pl.enc_y) : pl.lay[l - 1].x_out;
@@ -815,6 +823,7 @@ void suta_engine::build_plan(int B, long N) {
             for (int i = 0; i < k.nconv; ++i)
                 pl.lnpart_floats = std::max(pl.lnpart_floats,
                                             layernorm_bwd_conv_part_floats(B, pl.Lc[i], k.C[i], i == 0 ? 10 : 0));
+        if (k.stable && k.A > 0) pl.lnpart_floats = std::max(pl.lnpart_floats, adapter_part_floats(B, T, H));
         pl.lnpart = ar.take<float>((size_t)pl.lnpart_floats);
         pl.dpart = ar.take<double>((size_t)B * ((pl.Lc[0] + 127) / 128 + 2) * 2 * k.C[0] + (size_t)B * k.C[0] * 2);
         pl.c0part = ar.take<float>((size_t)B * ((pl.Lc[0] + 127) / 128) * k.K[0] * k.C[0] + 64);
@@ -1017,7 +1026,7 @@ void suta_engine::forward(int B) {
             });
             ffn_in = dead ? nullptr : lb.y2;
             ffn_res = lb.hmid;
-            ffn_out = lb.x_out;
+            ffn_out = k.A > 0 ? lb.ad_in : lb.x_out;  // (the adapter kernel writes x_out)
         } else {
             timed(F_NORM, [&] {
                 launch_layernorm_fwd(pl.rtmp, P + o_l1g[l], P + o_l1b[l], Pn, T, lb.y1, lb.xhat1, lb.rstd1, (int)BT, H,
@@ -1042,6 +1051,11 @@ void suta_engine::forward(int B) {
             add_resid(g, {ffn_res, H});
             gemm(g);
         }
+        if (k.stable && k.A > 0)  // x_out = h + adapter(h): h read once, the sum written once
+            timed(F_NORM, [&] {
+                launch_adapter_fwd(lb.ad_in, P + o_adg[l], P + o_adb[l], Pn, T, B, H, adw[l], 1e-5f, lb.x_out, lb.ad_mean,
+                                   lb.ad_rstd, st);
+            });
         if (!k.stable) {
             timed(F_NORM, [&] {
                 launch_layernorm_fwd(pl.rtmp, P + o_l2g[l], P + o_l2b[l], Pn, T, lb.x_out, lb.xhat2, lb.rstd2, (int)BT,
@@ -1140,6 +1154,13 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
             });
             dhres = t1;  // dr1
         } else {
+            if (k.A > 0) {  // through the adapter first: dh = dx + adapter-bwd(dx) (its plane P0 for du_gemm)
+                timed(F_NORM, [&] {
+                    launch_adapter_bwd(lb.ad_in, dx, lb.ad_mean, lb.ad_rstd, P + o_adg[l], P + o_adb[l], Pn, T, B, H,
+                                       adw[l], rT(), t1, G + o_adg[l], G + o_adb[l], Pn, pl.lnpart, st, P0);
+                });
+                std::swap(dx, t1);
+            }
             // du = (dx @ W2) * gelu'(u); dy2 = du @ W1; dhmid = LN2 bwd(dy2) + dx
             du_gemm(dx, l);
             void* dyp = dy_planes() ? plane(2) : nullptr;  // (plane 2's dctx of the layer above is consumed)
@@ -1736,6 +1757,10 @@ Cfg make_cfg(const suta_model_config* m) {
     c.posK = m->num_conv_pos_embeddings;
     c.posG = m->num_conv_pos_embedding_groups;
     c.eps = m->layer_norm_eps;
+    // HF builds the attention adapter in the stable-LN layer class only; the post-LN class ignores the field
+    c.A = c.stable ? m->adapter_attn_dim : 0;
+    if (c.A < 0) throw SutaError(SUTA_ERR_ARG, "adapter_attn_dim < 0");
+    if (c.A > 64) throw SutaError(SUTA_ERR_UNSUPPORTED, "adapter_attn_dim > 64 (the adapter kernels hold 1 <= A <= 64)");
     if (c.H % c.NH || c.H % c.posG) throw SutaError(SUTA_ERR_ARG, "hidden_size not divisible by heads/groups");
     // the conv-A GEMM's segmented-K loaders move 16-B chunks (4 floats; 8 bf16 on the planes), each inside one segment
     if ((c.H / c.posG) % 8) throw SutaError(SUTA_ERR_UNSUPPORTED, "pos-conv group width must be a multiple of 8");
@@ -1849,6 +1874,10 @@ int32_t suta_create(const suta_model_config* cfg, const char* const* names, cons
             e->o_l1b.push_back(add(b + "layer_norm.bias", {H}, false, true, true, 0));
             e->o_l2g.push_back(add(b + "final_layer_norm.weight", {H}, false, true, false, 0));
             e->o_l2b.push_back(add(b + "final_layer_norm.bias", {H}, false, true, true, 0));
+            if (c.A > 0) {  // the adapter's nn.LayerNorm: collect_params takes it like any other
+                e->o_adg.push_back(add(b + "adapter_layer.norm.weight", {H}, false, true, false, 0));
+                e->o_adb.push_back(add(b + "adapter_layer.norm.bias", {H}, false, true, true, 0));
+            }
         }
         e->Pn = rup(e->Pn, 64);
         std::vector<float> hp0(e->Pn, 0.f);
@@ -1892,6 +1921,39 @@ int32_t suta_create(const suta_model_config* cfg, const char* const* names, cons
             e->b1.push_back(up(b + "feed_forward.intermediate_dense.bias", c.F));
             e->w2.push_back(up(b + "feed_forward.output_dense.weight", (long)c.F * H));
             e->b2.push_back(up(b + "feed_forward.output_dense.bias", H));
+            if (c.A > 0) {  // zero-padded to [NA][Hp] / [Hp][NA], each linear in both orientations
+                const int A = c.A, NA = adapter_padded_width(A), Hp = (int)rup(H, 16);
+                const std::string a = b + "adapter_layer.";
+                const float* l1 = get(a + "linear_1.weight", (long)A * H);  // [A][H]
+                const float* l1b = get(a + "linear_1.bias", A);
+                const float* l2 = get(a + "linear_2.weight", (long)H * A);  // [H][A]
+                const float* l2b = get(a + "linear_2.bias", H);
+                std::vector<float> w1p((size_t)NA * Hp, 0.f), w1t((size_t)Hp * NA, 0.f), w2p((size_t)Hp * NA, 0.f),
+                    w2t((size_t)NA * Hp, 0.f), b1p(NA, 0.f), b2p(Hp, 0.f);
+                for (int n = 0; n < A; ++n)
+                    for (int h = 0; h < H; ++h) {
+                        w1p[(size_t)n * Hp + h] = w1t[(size_t)h * NA + n] = l1[(size_t)n * H + h];
+                        w2p[(size_t)h * NA + n] = w2t[(size_t)n * Hp + h] = l2[(size_t)h * A + n];
+                    }
+                std::copy(l1b, l1b + A, b1p.begin());
+                std::copy(l2b, l2b + H, b2p.begin());
+                auto upv = [&](const std::vector<float>& v) {
+                    float* dptr = e->dalloc((long)v.size());
+                    HIPCHK(hipMemcpy(dptr, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
+                    return dptr;
+                };
+                AdapterW aw{};
+                aw.w1 = upv(w1p);
+                aw.w1t = upv(w1t);
+                aw.w2 = upv(w2p);
+                aw.w2t = upv(w2t);
+                aw.b1 = upv(b1p);
+                aw.b2 = upv(b2p);
+                aw.A = A;
+                aw.NA = NA;
+                aw.Hp = Hp;
+                e->adw.push_back(aw);
+            }
         }
         e->wlm = up("lm_head.weight", (long)c.V * H);
         e->blm = up("lm_head.bias", c.V);

@@ -60,6 +60,30 @@ bool launch_layernorm_bwd_conv(const float* dy, const float* rstd, const float* 
 // Column sums per utterance: out[b][c] = sum_{t < rows} x[b][t][c]   (bias gradients).
 void launch_colsum(const float* x, int B, int rows, int C, float* out, long ostride, float* part, hipStream_t st);
 
+// MMS attention adapter of a stable-LN layer (adapter.hip): out = x + W2 relu(W1 LN(x) + b1) + b2, LN's gamma / beta
+// of utterance (row / rows_per_utt) at pstride, eps torch's LayerNorm default.  Exact fp32 on v_mfma_f32_16x16x4_f32.
+// The frozen linears come zero-padded (NA = adapter_padded_width(A): 16 for A <= 16, else 64; Hp = H rounded up to
+// 16) in both orientations:
+// w1 [NA][Hp] (linear_1.weight), w1t [Hp][NA] (its transpose), w2 [Hp][NA] (linear_2.weight), w2t [NA][Hp], b1 [NA],
+// b2 [Hp]; 1 <= A <= 64, H % 4 == 0, H <= 2048.
+struct AdapterW {
+    const float *w1, *w1t, *w2, *w2t, *b1, *b2;
+    int A, NA, Hp;
+};
+// fwd: stores the row means and rstd; x stays the backward's input, so out is a separate buffer
+void launch_adapter_fwd(const float* x, const float* g, const float* beta, long pstride, int rows_per_utt, int B, int H,
+                        const AdapterW& w, float eps, float* out, float* mean, float* rstd, hipStream_t st);
+// bwd: dx = dout + LN-bwd(W1^T ((W2^T dout) [z > 0])), x-hat and z recomputed from x; dgamma / dbeta (may be null)
+// per utterance at gstride, over the utterance's first tlen[u] frames (tlen null: all), summed through 16-row tile
+// partials in tile order (no atomics).  part: >= adapter_part_floats(B, rows_per_utt, H) floats.  dxb: optional bf16
+// copy of dx.
+int adapter_padded_width(int A);
+long adapter_part_floats(int B, int rows_per_utt, int H);
+void launch_adapter_bwd(const float* x, const float* dout, const float* mean, const float* rstd, const float* g,
+                        const float* beta, long pstride, int rows_per_utt, int B, int H, const AdapterW& w,
+                        const int* tlen, float* dx, float* dgamma, float* dbeta, long gstride, float* part,
+                        hipStream_t st, void* dxb = nullptr);
+
 // Flash-style fused attention (attn.hip), head dim 64, any T: forward writes ctx and the per-row
 // log-sum-exp lse[b][head][t] (no T x T matrix); backward recomputes P from lse and writes dQ, dK, dV
 // into dqkv's Q/K/V columns (dqp: flash_dq_scratch_floats floats of per-key-block dQ partials).
@@ -151,7 +175,7 @@ struct AdamRun {
     long start, len;
     int k;
 };
-#define SUTA_MAX_RUNS 24
+#define SUTA_MAX_RUNS 32
 #define ADAM_TAB 52  // floats per optimizer step in the device step table
 struct AdamArgs {
     int nruns;

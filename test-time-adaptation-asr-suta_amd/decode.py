@@ -42,13 +42,27 @@ def _token_name(v, default):
     return v if isinstance(v, str) else default
 
 
-def load_vocab(path: str) -> CTCVocab:
+def load_vocab(path: str, target_lang=None) -> CTCVocab:
     """The vocabulary of a local HF checkpoint directory: vocab.json (token -> id) and, where present, the pad,
-    word-delimiter and unk token names of tokenizer_config.json / special_tokens_map.json (HF defaults otherwise)."""
+    word-delimiter and unk token names of tokenizer_config.json / special_tokens_map.json (HF defaults otherwise).
+    A vocab.json nested per language ({"eng": {...}, ...}: MMS) gives `target_lang`'s table, else the one
+    tokenizer_config.json names as `target_lang`; a flat vocab.json ignores the argument."""
     import json
     import os
     with open(os.path.join(path, "vocab.json"), encoding="utf-8") as f:
         raw = json.load(f)
+    if raw and all(isinstance(v, dict) for v in raw.values()):
+        lang = target_lang
+        tc = os.path.join(path, "tokenizer_config.json")
+        if lang is None and os.path.isfile(tc):
+            with open(tc, encoding="utf-8") as f:
+                lang = json.load(f).get("target_lang")
+        if lang is None:
+            raise ValueError(f"{path}/vocab.json holds one vocabulary per language ({', '.join(sorted(raw)[:5])}, ...): "
+                             "pass --target_lang")
+        if lang not in raw:
+            raise KeyError(f"language '{lang}' is not in {path}/vocab.json ({', '.join(sorted(raw)[:8])}, ...)")
+        raw = raw[lang]
     n = max(raw.values()) + 1
     names = {"pad_token": "<pad>", "word_delimiter_token": WORD_DELIM, "unk_token": "<unk>"}
     for fn in ("special_tokens_map.json", "tokenizer_config.json"):   # the config wins, as in from_pretrained

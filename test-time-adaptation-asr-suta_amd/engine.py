@@ -31,7 +31,7 @@ class ModelConfigC(C.Structure):
                 ("conv_stride", C.c_int32 * MAX_CONV), ("conv_bias", C.c_int32),
                 ("feat_extract_norm_layer", C.c_int32), ("do_stable_layer_norm", C.c_int32),
                 ("num_conv_pos_embeddings", C.c_int32), ("num_conv_pos_embedding_groups", C.c_int32),
-                ("layer_norm_eps", C.c_float)]
+                ("layer_norm_eps", C.c_float), ("adapter_attn_dim", C.c_int32)]
 
 
 class HParamsC(C.Structure):
@@ -161,6 +161,7 @@ def config_to_c(cfg: dict) -> ModelConfigC:
     m.num_conv_pos_embeddings = cfg["num_conv_pos_embeddings"]
     m.num_conv_pos_embedding_groups = cfg["num_conv_pos_embedding_groups"]
     m.layer_norm_eps = cfg.get("layer_norm_eps", 1e-5)
+    m.adapter_attn_dim = int(cfg.get("adapter_attn_dim") or 0)   # 0 = none; ignored without do_stable_layer_norm
     return m
 
 

@@ -4,7 +4,7 @@ FLOPs_alg(N, S) = (S+1) * F(N) + S * B(N): the minimal schedule, 2 flops per MAC
 ops only (convs, linears, attention products).  Redundant re-forwards of the reference
 schedule are not credited.
 """
-from .config import frame_lengths
+from .config import adapter_dim, frame_lengths
 
 
 def forward_flops(cfg: dict, n_samples: int) -> float:
@@ -22,7 +22,8 @@ def forward_flops(cfg: dict, n_samples: int) -> float:
     lin = NL * T * (8.0 * H * H + 4.0 * H * F)
     att = NL * 4.0 * T * T * H
     head = 2.0 * T * H * V
-    return conv + proj + pos + lin + att + head
+    adapter = NL * T * 4.0 * H * adapter_dim(cfg)   # linear_1 and linear_2 of the attention adapter
+    return conv + proj + pos + lin + att + head + adapter
 
 
 def backward_flops(cfg: dict, n_samples: int) -> float:
@@ -41,7 +42,9 @@ def backward_flops(cfg: dict, n_samples: int) -> float:
         cin = 1 if i == 0 else C[i - 1]
         f = 2.0 * c * cin * k * L[i]
         conv += f if i == 0 else 2.0 * f             # conv0: dW only; conv1..: dW + dX
-    return head + lin + att + pos + proj + conv
+    # attention adapter: linear_1 recomputed, W2^T g and W1^T dz (dX only: both linears are frozen)
+    adapter = NL * T * 6.0 * H * adapter_dim(cfg)
+    return head + lin + att + pos + proj + conv + adapter
 
 
 def suta_flops(cfg: dict, n_samples: int, steps: int) -> float:

@@ -60,6 +60,10 @@ def build_parser(sdpl: bool = False):
         p.add_argument("--pl_coef", type=float, default=1)
     # engine-only options
     p.add_argument("--synthetic_weights", action="store_true", help="seeded random weights (no checkpoint)")
+    p.add_argument("--target_lang", type=str, default=None,
+                   help="MMS checkpoints (--asr <local dir> with adapter_attn_dim): overlay adapter.<LANG>.safetensors "
+                        "(attention adapters + that language's lm_head) and decode with the language's vocabulary, "
+                        "as HF's load_adapter / tokenizer.set_target_lang do")
     p.add_argument("--device", type=int, default=None)
     # defaults = the layout the headline bench measures (bench.py BATCH: 164 x 8 s = 1312 s of audio per call, about
     # 59 GB of workspace at 0.36 GB per 8 s utterance, of the 288 GB of HBM)
@@ -159,7 +163,9 @@ def workspace_bytes_per_audio_s(cfg, sdpl: bool = False, utt_s: float = 0.0) -> 
     attn = 0.0
     if not flash_attention_applies(cfg):  # P per layer and dP: NH T^2 fp32 per utterance = NH * 50 * 50 utt_s per second
         attn = (cfg["num_hidden_layers"] + 1) * cfg["num_attention_heads"] * 50 * 50 * 4 * float(utt_s)
-    return 50 * 4 * cfg["num_hidden_layers"] * 14 * cfg["hidden_size"] + 6350 * 512 * 4 * 3 + head + attn
+    from .config import adapter_dim
+    per_frame = 14 + (1 if adapter_dim(cfg) else 0)   # attention adapters save their input h per layer (section 2)
+    return 50 * 4 * cfg["num_hidden_layers"] * per_frame * cfg["hidden_size"] + 6350 * 512 * 4 * 3 + head + attn
 
 
 def engine_fixed_bytes(cfg, weights, max_batch: int, precision: str = "fp32") -> float:
@@ -194,11 +200,17 @@ def exp_name_of(a, sdpl: bool = False) -> str:
     return base + "_all_" + str(a.train_all) + "_LN_" + str(True)
 
 
-def load_model(asr: str, synthetic: bool):
+def load_model(asr: str, synthetic: bool, target_lang=None):
     from .config import get_config
-    from .weights import load_hf_checkpoint, synth_weights
+    from .weights import load_adapter, load_hf_checkpoint, synth_weights
     if os.path.isdir(asr):
-        return get_config(asr), load_hf_checkpoint(asr)
+        cfg, sd = get_config(asr), load_hf_checkpoint(asr)
+        if target_lang:
+            load_adapter(asr, target_lang, cfg, sd)
+        return cfg, sd
+    if target_lang:
+        raise RuntimeError(f"--target_lang {target_lang} needs --asr <local checkpoint directory> holding "
+                           f"adapter.{target_lang}.safetensors")
     try:
         from huggingface_hub import snapshot_download
         d = snapshot_download(asr, local_files_only=True)
@@ -256,7 +268,7 @@ def main(argv=None, sdpl: bool = False):
     vocab = pl_table = None
     if os.path.isfile(os.path.join(a.asr, "vocab.json")):   # --asr <local dir>: its own vocabulary (presets: built in)
         from .decode import load_vocab
-        vocab = load_vocab(a.asr)
+        vocab = load_vocab(a.asr, target_lang=a.target_lang)
     if sdpl:
         # main_SDPL.py:269-271 prints vocab.json: the reference opens the 960h table in its working directory; the
         # checkpoint's own is the one consistent reading for any other checkpoint
@@ -280,7 +292,7 @@ def main(argv=None, sdpl: bool = False):
                  f"train_feature = {a.train_feature}") + tail:
         say(line)
 
-    cfg, weights = load_model(a.asr, a.synthetic_weights)
+    cfg, weights = load_model(a.asr, a.synthetic_weights, a.target_lang)
     if vocab is not None:
         import functools
         from .decode import blank_notice

@@ -14,6 +14,8 @@ from __future__ import annotations
 
 from typing import List, Tuple
 
+from .config import adapter_dim
+
 # (name, is_layer_norm, own parameter names in registration order)
 Module = Tuple[str, bool, List[str]]
 
@@ -56,6 +58,11 @@ def named_modules(cfg: dict) -> List[Module]:
                 (ff + ".intermediate_dropout", False, []), (ff + ".intermediate_dense", False, ["weight", "bias"]),
                 (ff + ".intermediate_act_fn", False, []), (ff + ".output_dense", False, ["weight", "bias"]),
                 (ff + ".output_dropout", False, []), (lb + ".final_layer_norm", True, ["weight", "bias"])]
+        if adapter_dim(cfg):   # Wav2Vec2AttnAdapterLayer: norm (nn.LayerNorm), linear_1, act_fn, linear_2
+            ad = lb + ".adapter_layer"
+            out += [(ad, False, []), (ad + ".norm", True, ["weight", "bias"]),
+                    (ad + ".linear_1", False, ["weight", "bias"]), (ad + ".act_fn", False, []),
+                    (ad + ".linear_2", False, ["weight", "bias"])]
     out += [("dropout", False, []), ("lm_head", False, ["weight", "bias"])]
     return out
 

@@ -32,9 +32,9 @@ def synth_weights(cfg: dict, seed: int = DEFAULT_SEED, blank_bias: float = 1.0) 
         leaf = name.rsplit(".", 1)[-1]
         if name.endswith("masked_spec_embed"):
             a = rng.uniform(size=shape)
-        elif "layer_norm" in name and leaf == "weight":
+        elif ("layer_norm" in name or "adapter_layer.norm" in name) and leaf == "weight":
             a = 1.0 + 0.1 * n
-        elif "layer_norm" in name and leaf == "bias":
+        elif ("layer_norm" in name or "adapter_layer.norm" in name) and leaf == "bias":
             a = 0.1 * n
         elif leaf == "original0":                      # pos-conv weight_norm magnitude per tap
             H = cfg["hidden_size"]
@@ -81,3 +81,37 @@ def load_hf_checkpoint(path: str) -> Dict[str, np.ndarray]:
         sd = torch.load(pt, map_location="cpu", weights_only=True)
         return remap_legacy({k: v.float().numpy() for k, v in sd.items()})
     raise FileNotFoundError(f"no model.safetensors / pytorch_model.bin under {path}")
+
+
+def load_adapter(path: str, target_lang: str, cfg: dict, sd: Dict[str, np.ndarray]) -> None:
+    """Overlay a language's attention-adapter file of a LOCAL MMS checkpoint directory, as HF's
+    `Wav2Vec2PreTrainedModel.load_adapter` does: `adapter.<lang>.safetensors` (else `adapter.<lang>.bin`, loaded
+    weights_only) must hold exactly the adapter tensors of every layer plus `lm_head.weight` / `lm_head.bias`; they
+    replace `sd`'s, and `cfg["vocab_size"]` becomes the language's `lm_head.weight.shape[0]`.  In place."""
+    from .config import adapter_dim
+    if not adapter_dim(cfg):
+        raise ValueError(f"--target_lang {target_lang}: the checkpoint has no attention adapters "
+                         "(config.json: adapter_attn_dim with do_stable_layer_norm)")
+    st = os.path.join(path, f"adapter.{target_lang}.safetensors")
+    pt = os.path.join(path, f"adapter.{target_lang}.bin")
+    if os.path.isfile(st):
+        from safetensors.numpy import load_file
+        ad = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in load_file(st).items()}
+    elif os.path.isfile(pt):
+        import torch
+        ad = {k: v.float().numpy() for k, v in torch.load(pt, map_location="cpu", weights_only=True).items()}
+    else:
+        raise FileNotFoundError(f"no adapter.{target_lang}.safetensors / adapter.{target_lang}.bin under {path}")
+    shapes = dict(param_shapes(cfg))
+    want = {k for k in shapes if ".adapter_layer." in k} | {"lm_head.weight", "lm_head.bias"}
+    if set(ad) != want:
+        missing, extra = sorted(want - set(ad)), sorted(set(ad) - want)
+        raise ValueError(f"adapter file of '{target_lang}' does not match the model: missing {missing[:4]}"
+                         f"{' ...' if len(missing) > 4 else ''}, unexpected {extra[:4]}{' ...' if len(extra) > 4 else ''}")
+    V = int(ad["lm_head.weight"].shape[0])
+    for k, v in ad.items():
+        shape = (V,) + tuple(shapes[k][1:]) if k.startswith("lm_head.") else tuple(shapes[k])
+        if tuple(v.shape) != shape:
+            raise ValueError(f"adapter file of '{target_lang}': {k} has shape {tuple(v.shape)}, expected {shape}")
+        sd[k] = v
+    cfg["vocab_size"] = V
