@@ -8,6 +8,7 @@
  *   suta_create          Wav2Vec2ForCTC.from_pretrained(...).eval() + configure_model +
  *                        collect_params + setup_optimizer + copy_model_and_optimizer
  *                        (reference main.py:302-311, 8-23, 62-103, 137-145, 167-170)
+ *   suta_create_family   the same for HubertForCTC / Data2VecAudioForCTC checkpoints
  *   suta_reset           load_model_and_optimizer — episodic restore (main.py:147-155, 327-328)
  *   suta_forward         `model(input_values).logits` under no_grad (main.py:331-332)
  *   suta_step            forward_and_adapt(...) — one SUTA step, reference schedule
@@ -72,6 +73,25 @@ typedef struct suta_model_config {
     int32_t adapter_attn_dim;              /* 0 = none; MMS: 16 */
 } suta_model_config;
 
+/* The model family of a checkpoint (suta_create_family): HF's `model_type`.  It selects the state-dict prefix of the
+ * tensors the engine requires and of the names suta_param_info / suta_get_param take: `wav2vec2.`, `hubert.` or
+ * `data2vec_audio.`.  HuBERT (HubertForCTC) runs the wav2vec2 arithmetic.  data2vec-audio (Data2VecAudioForCTC)
+ * requires feat_extract_norm_layer 1 and do_stable_layer_norm 0 (else SUTA_ERR_ARG), ignores adapter_attn_dim, and
+ * its positional embedding is a stack of cfg->num_conv_pos_embeddings (1 .. 8) layers of grouped
+ * Conv1d(k = conv_pos_kernel_size in 1 .. 128, padding k / 2, bias; the last frame dropped when k is even) +
+ * LayerNorm(no affine, eps 1e-5) + GELU, added to its input; beyond those ranges SUTA_ERR_UNSUPPORTED.  The tensors
+ * "data2vec_audio.encoder.pos_conv_embed.layers.J.conv.{weight,bias}" are required and frozen.
+ * These fields live beside suta_model_config, not in it: that struct's layout is fixed (adapter_attn_dim is its last
+ * field). */
+typedef struct suta_model_family {
+    int32_t model_family;         /* SUTA_FAMILY_* */
+    int32_t conv_pos_kernel_size; /* data2vec-audio only: 19 */
+} suta_model_family;
+
+#define SUTA_FAMILY_WAV2VEC2 0
+#define SUTA_FAMILY_HUBERT 1
+#define SUTA_FAMILY_DATA2VEC_AUDIO 2
+
 /* forward_and_adapt / setup_optimizer / collect_params arguments (main.py:8-23, 62-103, 172-173)
  * and the CLI flags of main.py:221-241. */
 typedef struct suta_hparams {
@@ -125,6 +145,11 @@ typedef struct suta_hparams {
 int32_t suta_create(const suta_model_config* cfg, const char* const* names, const float* const* data,
                     const int64_t* numels, int32_t n, int32_t device, int32_t max_batch,
                     int64_t max_samples, suta_engine** out);
+
+/* suta_create for a checkpoint of any family; fam == NULL or all zero is suta_create (wav2vec2). */
+int32_t suta_create_family(const suta_model_config* cfg, const suta_model_family* fam, const char* const* names,
+                           const float* const* data, const int64_t* numels, int32_t n, int32_t device,
+                           int32_t max_batch, int64_t max_samples, suta_engine** out);
 
 int32_t suta_destroy(suta_engine* e);
 

@@ -43,6 +43,28 @@ _TINY_HD120 = dict(_TINY_HD80, hidden_size=240)
 _TINY_LAYER_A16 = dict(_TINY_LAYER, adapter_attn_dim=16)
 _TINY_HD80_A5 = dict(_TINY_HD80, adapter_attn_dim=5)
 
+# Model families (`model_type` of an HF config.json; absent = wav2vec2): the state-dict prefix of each.
+FAMILY_PREFIX = {"wav2vec2": "wav2vec2.", "hubert": "hubert.", "data2vec-audio": "data2vec_audio."}
+FAMILY_ID = {"wav2vec2": 0, "hubert": 1, "data2vec-audio": 2}   # suta_model_family.model_family
+
+# HuBERT (facebook/hubert-large-ls960-ft, hubert-xlarge-ls960-ft; HF HubertForCTC): the wav2vec2-large / XLS-R 1B body
+# under the key prefix `hubert.`.
+# data2vec-audio (facebook/data2vec-audio-base-960h, -large-960h; HF Data2VecAudioForCTC): layer-norm front end without
+# conv bias, post-LN encoder, and a positional embedding of `num_conv_pos_embeddings` layers (5) of grouped
+# Conv1d(k = conv_pos_kernel_size = 19) + LayerNorm(no affine) + GELU.  HF's Data2VecAudioConfig has neither
+# `feat_extract_norm` nor `do_stable_layer_norm`; they are set here to what its model classes do.
+# These geometries are quoted from memory and could not be verified offline; a checkpoint directory's config.json
+# governs.
+_HUBERT_LARGE = dict(_LARGE, model_type="hubert")
+_HUBERT_XLARGE = dict(_XLSR_1B, model_type="hubert")
+_D2V_BASE = dict(_BASE, model_type="data2vec-audio", feat_extract_norm="layer", do_stable_layer_norm=False,
+                 conv_bias=False, num_conv_pos_embeddings=5, conv_pos_kernel_size=19, num_conv_pos_embedding_groups=16)
+_D2V_LARGE = dict(_D2V_BASE, hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, intermediate_size=4096)
+_TINY_D2V = dict(_TINY_GROUP, model_type="data2vec-audio", feat_extract_norm="layer", do_stable_layer_norm=False,
+                 conv_bias=False, num_conv_pos_embeddings=5, conv_pos_kernel_size=19, num_conv_pos_embedding_groups=4)
+_TINY_D2V_EVEN = dict(_TINY_D2V, num_conv_pos_embeddings=2, conv_pos_kernel_size=4)   # even k: HF trims a frame
+_TINY_HUBERT = dict(_TINY_LAYER, model_type="hubert")
+
 PRESETS = {
     "facebook/wav2vec2-base-960h": _BASE,
     "wav2vec2-base": _BASE,
@@ -61,14 +83,36 @@ PRESETS = {
     "tiny-hd120": _TINY_HD120,
     "tiny-layer-a16": _TINY_LAYER_A16,
     "tiny-hd80-a5": _TINY_HD80_A5,
+    "facebook/hubert-large-ls960-ft": _HUBERT_LARGE,
+    "hubert-large": _HUBERT_LARGE,
+    "facebook/hubert-xlarge-ls960-ft": _HUBERT_XLARGE,
+    "hubert-xlarge": _HUBERT_XLARGE,
+    "facebook/data2vec-audio-base-960h": _D2V_BASE,
+    "data2vec-audio-base": _D2V_BASE,
+    "facebook/data2vec-audio-large-960h": _D2V_LARGE,
+    "data2vec-audio-large": _D2V_LARGE,
+    "tiny-d2v": _TINY_D2V,
+    "tiny-d2v-even": _TINY_D2V_EVEN,
+    "tiny-hubert": _TINY_HUBERT,
 }
+
+
+def family(cfg: dict) -> str:
+    """The model family of a geometry: "wav2vec2" (no `model_type` key), "hubert" or "data2vec-audio"."""
+    return cfg.get("model_type") or "wav2vec2"
+
+
+def prefix(cfg: dict) -> str:
+    """State-dict prefix of the family's base model (`wav2vec2.` / `hubert.` / `data2vec_audio.`)."""
+    return FAMILY_PREFIX[family(cfg)]
 
 
 def adapter_dim(cfg: dict) -> int:
     """Width A of the per-layer attention adapter (HF `adapter_attn_dim`), 0 for none.  HF builds the adapter only in
-    the stable-LN encoder layer (`Wav2Vec2EncoderLayerStableLayerNorm`); the post-LN layer class ignores the field."""
+    the stable-LN encoder layer (`Wav2Vec2EncoderLayerStableLayerNorm`); the post-LN layer class ignores the field,
+    and so do the HuBERT and data2vec-audio layer classes."""
     a = cfg.get("adapter_attn_dim")
-    return int(a) if a and cfg["do_stable_layer_norm"] else 0
+    return int(a) if a and cfg["do_stable_layer_norm"] and family(cfg) == "wav2vec2" else 0
 
 
 def head_dim(cfg: dict) -> int:
@@ -96,6 +140,23 @@ def get_config(name_or_path: str) -> dict:
                 cfg[k] = raw[k]
         if raw.get("adapter_attn_dim") is not None:   # MMS; absent or null: no adapters (the key stays out)
             cfg["adapter_attn_dim"] = int(raw["adapter_attn_dim"])
+        fam = raw.get("model_type") or "wav2vec2"
+        if fam not in FAMILY_PREFIX:
+            raise ValueError(f"{cfg_file}: model_type '{fam}' is not one of {sorted(FAMILY_PREFIX)}")
+        if fam == "hubert":
+            # HubertConfig's defaults: feat_extract_norm "group", do_stable_layer_norm False, as _BASE has them
+            if not raw.get("feat_proj_layer_norm", True):
+                raise ValueError(f"{cfg_file}: feat_proj_layer_norm false (hubert-base: no feature-projection "
+                                 "LayerNorm) is not implemented")
+            if raw.get("conv_pos_batch_norm", False):
+                raise ValueError(f"{cfg_file}: conv_pos_batch_norm true (BatchNorm positional conv) is not implemented")
+            cfg["model_type"] = fam
+        elif fam == "data2vec-audio":
+            # Data2VecAudioConfig has neither key: its conv layers are all LayerNorm ones, its encoder post-LN
+            cfg.update(model_type=fam, feat_extract_norm="layer", do_stable_layer_norm=False,
+                       num_conv_pos_embeddings=int(raw.get("num_conv_pos_embeddings", 5)),
+                       conv_pos_kernel_size=int(raw.get("conv_pos_kernel_size", 19)))
+            cfg.pop("adapter_attn_dim", None)
         return cfg
     raise KeyError(f"unknown model '{name_or_path}': not a preset and no config.json found")
 
@@ -114,30 +175,37 @@ def num_frames(cfg: dict, n_samples: int) -> int:
 
 
 def param_shapes(cfg: dict):
-    """(name, shape) of every Wav2Vec2ForCTC state_dict entry, in state_dict order."""
+    """(name, shape) of every state_dict entry of the family's ForCTC model (Wav2Vec2ForCTC, HubertForCTC,
+    Data2VecAudioForCTC), in state_dict order."""
     H, C = cfg["hidden_size"], cfg["conv_dim"]
-    out = [("wav2vec2.masked_spec_embed", (H,))]
+    pfx = prefix(cfg)
+    out = [(pfx + "masked_spec_embed", (H,))]
     group = cfg["feat_extract_norm"] == "group"
     for i, (c, k) in enumerate(zip(C, cfg["conv_kernel"])):
         cin = 1 if i == 0 else C[i - 1]
-        b = f"wav2vec2.feature_extractor.conv_layers.{i}."
+        b = f"{pfx}feature_extractor.conv_layers.{i}."
         out.append((b + "conv.weight", (c, cin, k)))
         if cfg["conv_bias"]:
             out.append((b + "conv.bias", (c,)))
         if (group and i == 0) or not group:
             out += [(b + "layer_norm.weight", (c,)), (b + "layer_norm.bias", (c,))]
-    fp = "wav2vec2.feature_projection."
+    fp = pfx + "feature_projection."
     out += [(fp + "layer_norm.weight", (C[-1],)), (fp + "layer_norm.bias", (C[-1],)),
             (fp + "projection.weight", (H, C[-1])), (fp + "projection.bias", (H,))]
     K, G = cfg["num_conv_pos_embeddings"], cfg["num_conv_pos_embedding_groups"]
-    pc = "wav2vec2.encoder.pos_conv_embed.conv."
-    out += [(pc + "bias", (H,)), (pc + "parametrizations.weight.original0", (1, 1, K)),
-            (pc + "parametrizations.weight.original1", (H, H // G, K))]
-    out += [("wav2vec2.encoder.layer_norm.weight", (H,)), ("wav2vec2.encoder.layer_norm.bias", (H,))]
+    if family(cfg) == "data2vec-audio":   # K layers of Conv1d(H, H, conv_pos_kernel_size, groups=G) with bias
+        for j in range(K):
+            pc = f"{pfx}encoder.pos_conv_embed.layers.{j}.conv."
+            out += [(pc + "weight", (H, H // G, cfg["conv_pos_kernel_size"])), (pc + "bias", (H,))]
+    else:
+        pc = pfx + "encoder.pos_conv_embed.conv."
+        out += [(pc + "bias", (H,)), (pc + "parametrizations.weight.original0", (1, 1, K)),
+                (pc + "parametrizations.weight.original1", (H, H // G, K))]
+    out += [(pfx + "encoder.layer_norm.weight", (H,)), (pfx + "encoder.layer_norm.bias", (H,))]
     F_ = cfg["intermediate_size"]
     A = adapter_dim(cfg)
     for li in range(cfg["num_hidden_layers"]):
-        lp = f"wav2vec2.encoder.layers.{li}."
+        lp = f"{pfx}encoder.layers.{li}."
         for pr in ("k_proj", "v_proj", "q_proj", "out_proj"):
             out += [(lp + f"attention.{pr}.weight", (H, H)), (lp + f"attention.{pr}.bias", (H,))]
         out += [(lp + "layer_norm.weight", (H,)), (lp + "layer_norm.bias", (H,)),

@@ -64,7 +64,13 @@ struct Cfg {
     int conv_bias, layer_mode, stable, posK, posG;
     int A;  // attention-adapter width of the stable-LN layers (MMS: 16); 0 = none
     float eps;
+    int family;  // SUTA_FAMILY_*: the state-dict prefix; data2vec-audio also the positional stack below
+    // data2vec-audio: the positional embedding is posD layers of grouped conv (posK taps each, posG groups) +
+    // LayerNorm(no affine) + GELU; 0 = the single weight-normed conv of posK taps (wav2vec2, HuBERT)
+    int posD;
 };
+constexpr int MAX_POS_STACK = 8;
+constexpr float POS_STACK_EPS = 1e-5f;  // HF builds the stack's nn.LayerNorm with torch's default eps
 
 // trainable tensor descriptor
 struct TP {
@@ -274,6 +280,9 @@ struct Plan {
     float *z[SUTA_MAX_CONV], *a[SUTA_MAX_CONV], *cxhat[SUTA_MAX_CONV], *crstd[SUTA_MAX_CONV], *cmean[SUTA_MAX_CONV];
     float *gn_mean, *gn_rstd;
     float *fp_xhat, *fp_rstd, *fp_y, *h0, *pz, *e, *enc_xhat, *enc_rstd, *enc_y;
+    // data2vec-audio positional stack: per layer the conv output z_j (the LayerNorm's input) and its row mean / rstd,
+    // kept for the backward; the layers' activations a_j ping-pong through two buffers (the last goes into e)
+    float *stk_z[MAX_POS_STACK], *stk_mean[MAX_POS_STACK], *stk_rstd[MAX_POS_STACK], *stk_a[2];
     float *fp_mean, *enc_mean;
     // LayerNorms whose input stays stored keep only the row means (x-hat recomputed in the backward):
     // the conv LNs of layer mode, the feature-projection LN, the encoder LN, and every LN of stable
@@ -309,6 +318,9 @@ struct suta_engine {
     // bf16 positional-conv weights [G][K][n][k] (fwd: n = c_out, k = c_in; bwd: taps flipped, n = c_in, k = c_out)
     // for posconv_bf16_kernel (group width 64); null otherwise
     void *wpos_bf_f = nullptr, *wpos_bf_b = nullptr;
+    // data2vec-audio positional stack (frozen, no weight norm): per layer the conv weights regrouped
+    // [G][posconv_stack_taps(posK)][Cg][Cg] in both orientations as wpos_f / wpos_b are (taps past posK zero), and the bias
+    std::vector<float*> wstk_f, wstk_b, bstk;
     // trainable
     std::vector<TP> tps;
     std::map<std::string, int> tpi;
@@ -590,6 +602,41 @@ struct suta_engine {
     // ... or bf16 mode, group width 64 (config C4): posconv_bf16_kernel (its forward and flipped-tap backward weights
     // wpos_bf_f / wpos_bf_b are built together)
     bool posconv_bf16() const { return posconv_kernel && bf16_mode() && wpos_bf_f && wpos_bf_b && c.posK % 4 == 0; }
+    // The stack's convs on the same kernel (its epilogue-free form, any kernel size): exact fp32 mode, group widths
+    // 48 / 64.  Every other mode and width runs them on the mode's conv-A GEMM; LayerNorm and GELU are fp32 always.
+    bool stack_on_kernel() const {
+        return posconv_kernel && gemm_mode == SUTA_PRECISION_FP32_MFMA && (c.H / c.posG == 48 || c.H / c.posG == 64);
+    }
+    // One conv of the stack.  fwd: out = conv_j(in) + bias_j; bwd: out = conv_j^T(in) (+ res), rows at or past the
+    // utterance's length written as 0.  Input rows at or past the length read as zero in both.
+    void stack_conv(bool fwd, int j, const float* in, const float* res, float* out) {
+        const int Cg = c.H / c.posG, Kp = posconv_stack_taps(c.posK);
+        const float* w = fwd ? wstk_f[j] : wstk_b[j];
+        if (stack_on_kernel()) {
+            // input window and output once (+ residual), the layer's weights once
+            const double bytes = 4.0 * ((double)plan.B * plan.T * c.H * (res ? 3 : 2) + (double)c.posK * Cg * c.H);
+            timed(F_GEMM, [&] {
+                if (!launch_posconv_stack(fwd, in, w, fwd ? bstk[j] : nullptr, res, out, plan.B, plan.T, c.H, c.posG,
+                                          c.posK, rT(), st))
+                    throw SutaError(SUTA_ERR_UNSUPPORTED, "positional conv shape");
+            }, timing ? bytes : 0.0);
+            return;
+        }
+        auto group = [&](const float* p) { return Mat{p, c.H, Cg, (long)plan.T * c.H}; };
+        GemmParams g = batched(plan.T, Cg, c.posK * Cg, group(in), 0, {w, Cg, (long)Kp * Cg * Cg, 0}, 0, group(out),
+                               plan.B * c.posG, c.posG);
+        g.segK = Cg;
+        g.pad = fwd ? c.posK / 2 : c.posK - 1 - c.posK / 2;
+        g.Mvalid = plan.T;
+        g.zmvalid = rT();
+        if (res) add_resid(g, group(res));
+        if (fwd) add_bias(g, bstk[j], Cg);
+        else if (plan.ragged) {
+            g.epi |= EPI_ROWMASK;
+            g.zrows = rT();
+        }
+        gemm(g);
+    }
     void build_weight_planes();
     // whether gemm(p0) takes the 256 x 256 bf16-plane kernel's C^T epilogue (the producer's A plane given, B a frozen
     // weight with planes): the condition for fusing EPI_DELTA into it
@@ -767,7 +814,14 @@ void suta_engine::build_plan(int B, long N) {
         pl.fp_rstd = ar.take<float>(BT);
         pl.fp_y = ar.take<float>(BT * C6);
         pl.h0 = ar.take<float>(BT * H);
-        pl.pz = ar.take<float>(BT * H);
+        pl.pz = k.posD ? nullptr : ar.take<float>(BT * H);
+        for (int j = 0; j < MAX_POS_STACK; ++j) {
+            const bool on = j < k.posD;
+            pl.stk_z[j] = on ? ar.take<float>(BT * H) : nullptr;
+            pl.stk_mean[j] = on ? ar.take<float>(BT) : nullptr;
+            pl.stk_rstd[j] = on ? ar.take<float>(BT) : nullptr;
+        }
+        for (int j = 0; j < 2; ++j) pl.stk_a[j] = k.posD > 1 ? ar.take<float>(BT * H) : nullptr;
         pl.e = ar.take<float>(BT * H);
         pl.enc_xhat = nullptr;
         pl.enc_mean = ar.take<float>(BT);
@@ -946,9 +1000,24 @@ void suta_engine::forward(int B) {
         add_bias(g, P + o_pb, 0, Pn);
         gemm(g);
     }
+    // data2vec-audio: e = h0 + stack(h0), a layer = conv + bias -> LayerNorm(no affine) -> GELU; z_j and the row
+    // statistics stay for the backward, the last layer's row kernel adds h0
+    if (k.posD) {
+        const float* in = pl.h0;
+        for (int j = 0; j < k.posD; ++j) {
+            const bool last = j + 1 == k.posD;
+            float* out = last ? pl.e : pl.stk_a[j & 1];
+            stack_conv(true, j, in, nullptr, pl.stk_z[j]);
+            timed(F_NORM, [&] {
+                launch_ln_gelu_fwd(pl.stk_z[j], last ? pl.h0 : nullptr, out, pl.stk_mean[j], pl.stk_rstd[j], (int)BT, T,
+                                   H, POS_STACK_EPS, rT(), st);
+            }, 4.0 * BT * H * (last ? 3 : 2));
+            in = out;
+        }
+    }
     // positional conv: e = h0 + gelu(posconv(h0)); pz = pre-activation
     // dedicated kernel in exact fp32 mode for group widths 48 / 64 (timed with the MFMA contractions)
-    if (posconv_fp32_kernel())
+    else if (posconv_fp32_kernel())
         timed(F_GEMM, [&] {
             if (!launch_posconv(true, pl.h0, wpos_f, bpos, pl.h0, pl.e, pl.pz, B, T, H, k.posG, k.posK, k.posK / 2,
                                 rT(), st))
@@ -1267,9 +1336,20 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
         dpz = pl.d1;
         dh0 = pl.d2;
     }
-    timed(F_EW, [&] { launch_dgelu_mul(de, pl.pz, dpz, BT * H, st); });
+    if (!k.posD) timed(F_EW, [&] { launch_dgelu_mul(de, pl.pz, dpz, BT * H, st); });
     // dh0 = posconv^T(dpz) + de: the forward's kernel choice, on the flipped taps
-    if (posconv_fp32_kernel())
+    if (k.posD) {
+        // data2vec-audio: dz_j = LayerNorm/GELU backward of da_j (da of the last layer = de), da_{j-1} = conv_j^T(dz_j)
+        // on the flipped taps; dh0 = conv_0^T(dz_0) + de
+        const float* da = de;
+        for (int j = k.posD - 1; j >= 0; --j) {
+            timed(F_NORM, [&] {
+                launch_ln_gelu_bwd(da, pl.stk_z[j], pl.stk_mean[j], pl.stk_rstd[j], dpz, (int)BT, T, H, rT(), st);
+            }, 4.0 * BT * H * 3);
+            stack_conv(false, j, dpz, j == 0 ? de : nullptr, dh0);
+            da = dh0;
+        }
+    } else if (posconv_fp32_kernel())
         timed(F_GEMM, [&] {
             if (!launch_posconv(false, dpz, wpos_b, nullptr, de, dh0, nullptr, B, T, H, k.posG, k.posK,
                                 k.posK - 1 - k.posK / 2, rT(), st))
@@ -1735,7 +1815,7 @@ int32_t guard(Fn&& fn) {
     }
 }
 
-Cfg make_cfg(const suta_model_config* m) {
+Cfg make_cfg(const suta_model_config* m, const suta_model_family* fam) {
     Cfg c{};
     c.H = m->hidden_size;
     c.L = m->num_hidden_layers;
@@ -1757,8 +1837,23 @@ Cfg make_cfg(const suta_model_config* m) {
     c.posK = m->num_conv_pos_embeddings;
     c.posG = m->num_conv_pos_embedding_groups;
     c.eps = m->layer_norm_eps;
-    // HF builds the attention adapter in the stable-LN layer class only; the post-LN class ignores the field
-    c.A = c.stable ? m->adapter_attn_dim : 0;
+    c.family = fam ? fam->model_family : SUTA_FAMILY_WAV2VEC2;
+    if (c.family < SUTA_FAMILY_WAV2VEC2 || c.family > SUTA_FAMILY_DATA2VEC_AUDIO)
+        throw SutaError(SUTA_ERR_ARG, "model_family is none of SUTA_FAMILY_*");
+    c.posD = 0;
+    if (c.family == SUTA_FAMILY_DATA2VEC_AUDIO) {
+        if (!c.layer_mode) throw SutaError(SUTA_ERR_ARG, "data2vec-audio requires feat_extract_norm_layer = 1");
+        if (c.stable) throw SutaError(SUTA_ERR_ARG, "data2vec-audio requires do_stable_layer_norm = 0");
+        c.posD = m->num_conv_pos_embeddings;
+        c.posK = fam->conv_pos_kernel_size;
+        if (c.posD < 1 || c.posD > MAX_POS_STACK)
+            throw SutaError(SUTA_ERR_UNSUPPORTED, "data2vec-audio: num_conv_pos_embeddings (the stack's depth) outside 1 .. 8");
+        if (c.posK < 1 || c.posK > 128)
+            throw SutaError(SUTA_ERR_UNSUPPORTED, "data2vec-audio: conv_pos_kernel_size outside 1 .. 128");
+    }
+    // HF builds the attention adapter in wav2vec2's stable-LN layer class only; the post-LN class and the other
+    // families ignore the field
+    c.A = (c.stable && c.family == SUTA_FAMILY_WAV2VEC2) ? m->adapter_attn_dim : 0;
     if (c.A < 0) throw SutaError(SUTA_ERR_ARG, "adapter_attn_dim < 0");
     if (c.A > 64) throw SutaError(SUTA_ERR_UNSUPPORTED, "adapter_attn_dim > 64 (the adapter kernels hold 1 <= A <= 64)");
     if (c.H % c.NH || c.H % c.posG) throw SutaError(SUTA_ERR_ARG, "hidden_size not divisible by heads/groups");
@@ -1790,10 +1885,16 @@ int32_t suta_num_frames(const suta_model_config* cfg, int64_t n, int64_t* out) {
 int32_t suta_create(const suta_model_config* cfg, const char* const* names, const float* const* data,
                     const int64_t* numels, int32_t n, int32_t device, int32_t max_batch, int64_t max_samples,
                     suta_engine** out) {
+    return suta_create_family(cfg, nullptr, names, data, numels, n, device, max_batch, max_samples, out);
+}
+
+int32_t suta_create_family(const suta_model_config* cfg, const suta_model_family* fam, const char* const* names,
+                           const float* const* data, const int64_t* numels, int32_t n, int32_t device,
+                           int32_t max_batch, int64_t max_samples, suta_engine** out) {
     return guard([&] {
         if (!cfg || !out || max_batch < 1) throw SutaError(SUTA_ERR_ARG, "null argument");
         std::unique_ptr<suta_engine> e(new suta_engine());
-        e->c = make_cfg(cfg);
+        e->c = make_cfg(cfg, fam);
         const Cfg& c = e->c;
         e->device = device;
         e->max_batch = max_batch;
@@ -1824,7 +1925,9 @@ int32_t suta_create(const suta_model_config* cfg, const char* const* names, cons
             HIPCHK(hipMemcpy(dptr, h, numel * sizeof(float), hipMemcpyHostToDevice));
             return dptr;
         };
-        const std::string pfx = "wav2vec2.";
+        const std::string pfx = c.family == SUTA_FAMILY_HUBERT           ? "hubert."
+                                : c.family == SUTA_FAMILY_DATA2VEC_AUDIO ? "data2vec_audio."
+                                                                         : "wav2vec2.";
         const int H = c.H;
         // ---- trainable layout ----
         auto add = [&](const std::string& nm, std::vector<long> shape, bool conv_w, bool ln, bool bias, int depth) {
@@ -1957,8 +2060,30 @@ int32_t suta_create(const suta_model_config* cfg, const char* const* names, cons
         }
         e->wlm = up("lm_head.weight", (long)c.V * H);
         e->blm = up("lm_head.bias", c.V);
+        // ---- data2vec-audio positional stack: plain grouped convs, regrouped as below, zero taps appended ----
+        for (int j = 0; j < c.posD; ++j) {
+            const int K = c.posK, Kp = posconv_stack_taps(K), G = c.posG, Cg = H / G;
+            const std::string b = pfx + "encoder.pos_conv_embed.layers." + std::to_string(j) + ".conv.";
+            const float* v = get(b + "weight", (long)H * Cg * K);
+            std::vector<float> wf((size_t)G * Kp * Cg * Cg, 0.f), wb((size_t)G * Kp * Cg * Cg, 0.f);
+            for (int gi = 0; gi < G; ++gi)
+                for (int co = 0; co < Cg; ++co)
+                    for (int ci = 0; ci < Cg; ++ci)
+                        for (int q = 0; q < K; ++q) {
+                            const float wv = v[(((long)gi * Cg + co) * Cg + ci) * K + q];
+                            wf[(((size_t)gi * Kp + q) * Cg + ci) * Cg + co] = wv;
+                            wb[(((size_t)gi * Kp + (K - 1 - q)) * Cg + co) * Cg + ci] = wv;
+                        }
+            float* df = e->dalloc((long)wf.size());
+            float* db = e->dalloc((long)wb.size());
+            HIPCHK(hipMemcpy(df, wf.data(), wf.size() * 4, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(db, wb.data(), wb.size() * 4, hipMemcpyHostToDevice));
+            e->wstk_f.push_back(df);
+            e->wstk_b.push_back(db);
+            e->bstk.push_back(up(b + "bias", H));
+        }
         // ---- positional conv: weight norm (dim=2) precomputed, regrouped for the conv-A GEMM ----
-        {
+        if (!c.posD) {
             const int K = c.posK, G = c.posG, Cg = H / G;
             const std::string b = pfx + "encoder.pos_conv_embed.conv.";
             const float* g = get(b + "parametrizations.weight.original0", K);

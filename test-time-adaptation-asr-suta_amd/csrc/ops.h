@@ -115,6 +115,19 @@ bool launch_flash_wide_bwd(const float* qkv, const float* dctx, const float* lse
 // bwd: C = conv + R (rows >= tlen -> 0).  false (nothing launched) outside the supported shapes
 bool launch_posconv(bool fwd, const float* x, const float* W, const float* bias, const float* R, float* C, float* C2,
                     int B, int T, int H, int G, int K, int pad, const int* tlen, hipStream_t st);
+// One conv of data2vec-audio's positional stack on the same kernel, any K >= 1: W = [G][posconv_stack_taps(K)][CG][CG]
+// with the taps past K zero (the kernel streams taps in pairs).  fwd: C = conv + bias (pad K / 2); bwd: W the flipped
+// taps, pad K - 1 - K / 2, C = conv (+ R when given), rows >= tlen -> 0.  Input rows >= tlen read as zero in both.
+int posconv_stack_taps(int K);
+bool launch_posconv_stack(bool fwd, const float* x, const float* W, const float* bias, const float* R, float* C, int B,
+                          int T, int H, int G, int K, const int* tlen, hipStream_t st);
+// LayerNorm(no affine) -> GELU of the stack's rows (D <= 2048; one wave per row).  fwd: a = gelu(xhat) (+ resid when
+// given), row mean / rstd stored; bwd: dz = rstd * (dy - mean(dy) - xhat * mean(dy * xhat)), dy = da * gelu'(xhat),
+// xhat recomputed from z.  Rows >= tlen[row / rows_per_utt] (tlen may be null) are written as 0 (fwd: resid alone).
+void launch_ln_gelu_fwd(const float* z, const float* resid, float* a, float* mean, float* rstd, int rows,
+                        int rows_per_utt, int D, float eps, const int* tlen, hipStream_t st);
+void launch_ln_gelu_bwd(const float* da, const float* z, const float* mean, const float* rstd, float* dz, int rows,
+                        int rows_per_utt, int D, const int* tlen, hipStream_t st);
 // bf16 mode, group width 64: Wt = bf16 weights [G][K][n][k] (n = output channel, k = input channel)
 bool launch_posconv_bf16(bool fwd, const float* x, const void* Wt, const float* bias, const float* R, float* C,
                          float* C2, int B, int T, int H, int G, int K, int pad, const int* tlen, hipStream_t st);

@@ -358,6 +358,101 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// data2vec-audio positional stack: LayerNorm(no affine) -> GELU over D (<= 2048), one wave per row, the layout of
+// layernorm_fwd_kernel.  Rows at or past the utterance's length (tlen, may be null) are written as 0 in both
+// directions, so the next layer's conv sees zero padding there and no gradient leaves them.
+//   fwd: a = gelu(xhat) (+ resid: the stack's last layer adds the stack's input), mean and rstd stored
+//   bwd: dy = da * gelu'(xhat), dz = rstd * (dy - mean(dy) - xhat * mean(dy * xhat)); xhat recomputed from z
+// ------------------------------------------------------------------------------------------
+template <int NPL>
+__global__ __launch_bounds__(256) void ln_gelu_fwd_kernel(const float* __restrict__ z, const float* __restrict__ resid,
+                                                          float* __restrict__ a, float* __restrict__ meanp,
+                                                          float* __restrict__ rstd, int rows, int rows_per_utt, int D,
+                                                          float eps, const int* __restrict__ tlen) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int u = (int)(row / rows_per_utt);
+    const bool valid = !tlen || (int)(row - (long)u * rows_per_utt) < tlen[u];
+    const float* zr = z + row * D;
+    float v[NPL];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) {
+        const int c = lane + i * 64;
+        v[i] = (valid && c < D) ? zr[c] : 0.f;
+        s += v[i];
+    }
+    s = wave_sum(s);
+    const float mean = s / D;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) {
+        const int c = lane + i * 64;
+        const float d = c < D ? v[i] - mean : 0.f;
+        q += d * d;
+    }
+    q = wave_sum(q);
+    const float rs = 1.0f / sqrtf(q / D + eps);
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) {
+        const int c = lane + i * 64;
+        if (c < D) {
+            float o = valid ? gelu_f((v[i] - mean) * rs) : 0.f;
+            if (resid) o += resid[row * D + c];
+            a[row * D + c] = o;
+        }
+    }
+    if (lane == 0) {
+        rstd[row] = rs;
+        meanp[row] = mean;
+    }
+}
+
+template <int NPL>
+__global__ __launch_bounds__(256) void ln_gelu_bwd_kernel(const float* __restrict__ da, const float* __restrict__ z,
+                                                          const float* __restrict__ meanp,
+                                                          const float* __restrict__ rstd, float* __restrict__ dz,
+                                                          int rows, int rows_per_utt, int D,
+                                                          const int* __restrict__ tlen) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int u = (int)(row / rows_per_utt);
+    const bool valid = !tlen || (int)(row - (long)u * rows_per_utt) < tlen[u];
+    if (!valid) {
+        for (int c = lane; c < D; c += 64) dz[row * D + c] = 0.f;
+        return;
+    }
+    const float mean = meanp[row], rs = rstd[row];
+    float xh[NPL], dy[NPL];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) {  // all loads first; columns past D hold xhat = 0, dy = 0
+        const int c = lane + i * 64;
+        xh[i] = c < D ? z[row * D + c] : mean;
+        dy[i] = c < D ? da[row * D + c] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) {
+        xh[i] = (xh[i] - mean) * rs;
+        dy[i] *= dgelu_f(xh[i]);
+        s1 += dy[i];
+        s2 += dy[i] * xh[i];
+        // erff's polynomial takes ~20 registers per element in flight: without the fence the scheduler interleaves
+        // all NPL of them (176 VGPRs at NPL = 16, scratch at 32)
+        if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+    }
+    s1 = wave_sum(s1) / D;
+    s2 = wave_sum(s2) / D;
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) {
+        const int c = lane + i * 64;
+        if (c < D) dz[row * D + c] = rs * (dy[i] - s1 - xh[i] * s2);
+    }
+}
+
 constexpr int LNB_ROWS = 16;
 template <int NPL>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ xhat,
@@ -854,6 +949,10 @@ __global__ __launch_bounds__(256) void colsum_partial(const float* __restrict__ 
 // weights stream through two LDS buffers of CHT taps (register-staged, one barrier per chunk), and
 // each wave runs exact-fp32 v_mfma_f32_16x16x4_f32 on its 16 frames x CG channels (CG/16 fragments).
 //   FWD: C = R + gelu(acc + bias), C2 = acc + bias (pre-activation);  BWD: C = acc + R, rows >= len -> 0
+//   STK (a layer of data2vec-audio's positional stack; LayerNorm and GELU follow in ln_gelu_fwd_kernel):
+//   FWD: C = acc + bias only;  BWD: C = acc (+ R when given: the layer nearest the stack's input), rows >= len -> 0
+// K is a multiple of CHT: a kernel size that is not (data2vec's 19) comes with zero taps appended to the weights
+// (launch_posconv_stack), whose window rows exist and contribute nothing.
 // Blocks of one group run on one XCD (its weights stay in that L2).
 // ------------------------------------------------------------------------------------------
 template <int CG>
@@ -862,7 +961,7 @@ struct PcLayout {
     static constexpr int WS = (CG % 64 == 0) ? CG + 16 : CG;  // weight row stride (conflict-free B reads)
 };
 
-template <int CG, int WB, int CHT, bool FWD>
+template <int CG, int WB, int CHT, bool FWD, bool STK = false>
 __global__ __launch_bounds__(WB * 64, 1) void posconv_kernel(const float* __restrict__ x, const float* __restrict__ W,
                                                              const float* __restrict__ bias,
                                                              const float* __restrict__ R, float* __restrict__ C,
@@ -961,10 +1060,13 @@ __global__ __launch_bounds__(WB * 64, 1) void posconv_kernel(const float* __rest
             float v;
             if (FWD) {
                 v = acc[nf][i] * 1.0f + bias[gi * CG + co];
-                C2[o + co] = v;
-                v = gelu_f(v) + R[o + co];
+                if (!STK) {
+                    C2[o + co] = v;
+                    v = gelu_f(v) + R[o + co];
+                }
             } else {
-                v = acc[nf][i] + R[o + co];
+                v = acc[nf][i];
+                if (!STK || R) v += R[o + co];
                 if (tlen && t >= tl) v = 0.f;
             }
             C[o + co] = v;
@@ -2078,17 +2180,17 @@ constexpr int PC_CHT = 2;  // taps per weight chunk: two chunks + the base windo
         if ((x) != hipSuccess) throw std::runtime_error("hipFuncSetAttribute(posconv) failed"); \
     } while (0)
 
-template <int CG, bool FWD>
+template <int CG, bool FWD, bool STK>
 static void posconv_go(int WB, dim3 grid, size_t lds, hipStream_t st, const float* x, const float* W,
                        const float* bias, const float* R, float* C, float* C2, int T, int H, int G, int K, int pad,
                        const int* tlen, int ntile, int B) {
     // > 64 KiB of dynamic LDS must be allowed per kernel (once per instantiation)
 #define PC(WB_)                                                                                                   \
     do {                                                                                                          \
-        set_max_lds_once(reinterpret_cast<const void*>(&posconv_kernel<CG, WB_, PC_CHT, FWD>), 160 * 1024,       \
+        set_max_lds_once(reinterpret_cast<const void*>(&posconv_kernel<CG, WB_, PC_CHT, FWD, STK>), 160 * 1024,  \
                          "posconv_kernel");                                                                       \
-        hipLaunchKernelGGL((posconv_kernel<CG, WB_, PC_CHT, FWD>), grid, dim3(WB_ * 64), lds, st, x, W, bias, R, C, \
-                           C2, T, H, G, K, pad, tlen, ntile, B);                                                  \
+        hipLaunchKernelGGL((posconv_kernel<CG, WB_, PC_CHT, FWD, STK>), grid, dim3(WB_ * 64), lds, st, x, W, bias, \
+                           R, C, C2, T, H, G, K, pad, tlen, ntile, B);                                            \
     } while (0)
     switch (WB) {
         case 4: PC(4); break;
@@ -2100,8 +2202,9 @@ static void posconv_go(int WB, dim3 grid, size_t lds, hipStream_t st, const floa
 #undef PC
 }
 
-bool launch_posconv(bool fwd, const float* x, const float* W, const float* bias, const float* R, float* C, float* C2,
-                    int B, int T, int H, int G, int K, int pad, const int* tlen, hipStream_t st) {
+template <bool STK>
+static bool posconv_launch(bool fwd, const float* x, const float* W, const float* bias, const float* R, float* C,
+                           float* C2, int B, int T, int H, int G, int K, int pad, const int* tlen, hipStream_t st) {
     const int CG = H / G;
     if ((CG != 48 && CG != 64) || K % PC_CHT || H % 4) return false;
     // waves per block: fewest padded frames over ceil(T / (16 WB)) tiles (T = 399 -> 5 waves, 400 rows)
@@ -2121,13 +2224,62 @@ bool launch_posconv(bool fwd, const float* x, const float* W, const float* bias,
     if (lds > 160 * 1024) return false;
     const dim3 grid((unsigned)((long)G * B * ntile));
     if (CG == 48) {
-        if (fwd) posconv_go<48, true>(WB, grid, lds, st, x, W, bias, R, C, C2, T, H, G, K, pad, tlen, ntile, B);
-        else posconv_go<48, false>(WB, grid, lds, st, x, W, bias, R, C, C2, T, H, G, K, pad, tlen, ntile, B);
+        if (fwd) posconv_go<48, true, STK>(WB, grid, lds, st, x, W, bias, R, C, C2, T, H, G, K, pad, tlen, ntile, B);
+        else posconv_go<48, false, STK>(WB, grid, lds, st, x, W, bias, R, C, C2, T, H, G, K, pad, tlen, ntile, B);
     } else {
-        if (fwd) posconv_go<64, true>(WB, grid, lds, st, x, W, bias, R, C, C2, T, H, G, K, pad, tlen, ntile, B);
-        else posconv_go<64, false>(WB, grid, lds, st, x, W, bias, R, C, C2, T, H, G, K, pad, tlen, ntile, B);
+        if (fwd) posconv_go<64, true, STK>(WB, grid, lds, st, x, W, bias, R, C, C2, T, H, G, K, pad, tlen, ntile, B);
+        else posconv_go<64, false, STK>(WB, grid, lds, st, x, W, bias, R, C, C2, T, H, G, K, pad, tlen, ntile, B);
     }
     return true;
+}
+
+bool launch_posconv(bool fwd, const float* x, const float* W, const float* bias, const float* R, float* C, float* C2,
+                    int B, int T, int H, int G, int K, int pad, const int* tlen, hipStream_t st) {
+    return posconv_launch<false>(fwd, x, W, bias, R, C, C2, B, T, H, G, K, pad, tlen, st);
+}
+
+int posconv_stack_taps(int K) { return (K + PC_CHT - 1) / PC_CHT * PC_CHT; }
+
+bool launch_posconv_stack(bool fwd, const float* x, const float* W, const float* bias, const float* R, float* C, int B,
+                          int T, int H, int G, int K, const int* tlen, hipStream_t st) {
+    if (K < 1 || (fwd && !bias)) return false;
+    // forward taps reach K / 2 frames back (HF pads K / 2 and drops the last frame of an even K), the flipped taps
+    // of the backward K - 1 - K / 2; the appended zero taps lie past the last real one in both
+    return posconv_launch<true>(fwd, x, W, bias, R, C, nullptr, B, T, H, G, posconv_stack_taps(K),
+                                fwd ? K / 2 : K - 1 - K / 2, tlen, st);
+}
+
+static void ln_gelu_grid(int rows, int D, dim3& grid, int& npl) {
+    grid = dim3((unsigned)((rows + 3) / 4));
+    npl = D <= 256 ? 4 : D <= 512 ? 8 : D <= 1024 ? 16 : 32;
+}
+
+void launch_ln_gelu_fwd(const float* z, const float* resid, float* a, float* mean, float* rstd, int rows,
+                        int rows_per_utt, int D, float eps, const int* tlen, hipStream_t st) {
+    if (D > 2048) throw std::runtime_error("launch_ln_gelu_fwd: D > 2048");
+    dim3 grid;
+    int npl;
+    ln_gelu_grid(rows, D, grid, npl);
+#define LG(N) hipLaunchKernelGGL(ln_gelu_fwd_kernel<N>, grid, dim3(256), 0, st, z, resid, a, mean, rstd, rows, rows_per_utt, D, eps, tlen)
+    if (npl == 4) LG(4);
+    else if (npl == 8) LG(8);
+    else if (npl == 16) LG(16);
+    else LG(32);
+#undef LG
+}
+
+void launch_ln_gelu_bwd(const float* da, const float* z, const float* mean, const float* rstd, float* dz, int rows,
+                        int rows_per_utt, int D, const int* tlen, hipStream_t st) {
+    if (D > 2048) throw std::runtime_error("launch_ln_gelu_bwd: D > 2048");
+    dim3 grid;
+    int npl;
+    ln_gelu_grid(rows, D, grid, npl);
+#define LG(N) hipLaunchKernelGGL(ln_gelu_bwd_kernel<N>, grid, dim3(256), 0, st, da, z, mean, rstd, dz, rows, rows_per_utt, D, tlen)
+    if (npl == 4) LG(4);
+    else if (npl == 8) LG(8);
+    else if (npl == 16) LG(16);
+    else LG(32);
+#undef LG
 }
 
 template <bool FWD>

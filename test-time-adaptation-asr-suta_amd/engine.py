@@ -12,13 +12,13 @@ from typing import Dict, Iterable, List, Optional, Sequence
 
 import numpy as np
 
-from .config import param_shapes
+from .config import FAMILY_ID, family, param_shapes
 
 LIB_PATH = os.environ.get("SUTA_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsuta.so")
 MAX_CONV = 8
 
 # exported symbols (kept in sync with include/suta.h; tests/test_abi.py checks both)
-EXPORTS = ("suta_create", "suta_destroy", "suta_reset", "suta_num_frames", "suta_forward", "suta_step", "suta_step_ex",
+EXPORTS = ("suta_create", "suta_create_family", "suta_destroy", "suta_reset", "suta_num_frames", "suta_forward", "suta_step", "suta_step_ex",
            "suta_adapt", "suta_adapt_varlen", "suta_loss_grad", "suta_set_pseudo_labels", "suta_get_param", "suta_param_info", "suta_sync", "suta_stream", "suta_set_timing",
            "suta_get_timing", "suta_get_timing_ex", "suta_set_precision", "suta_set_graphs", "suta_set_census",
            "suta_get_census", "suta_get_graph_stats", "suta_get_workspace_bytes", "suta_last_error")
@@ -32,6 +32,10 @@ class ModelConfigC(C.Structure):
                 ("feat_extract_norm_layer", C.c_int32), ("do_stable_layer_norm", C.c_int32),
                 ("num_conv_pos_embeddings", C.c_int32), ("num_conv_pos_embedding_groups", C.c_int32),
                 ("layer_norm_eps", C.c_float), ("adapter_attn_dim", C.c_int32)]
+
+
+class ModelFamilyC(C.Structure):   # suta_model_family: beside suta_model_config, whose layout is fixed
+    _fields_ = [("model_family", C.c_int32), ("conv_pos_kernel_size", C.c_int32)]
 
 
 class HParamsC(C.Structure):
@@ -93,6 +97,7 @@ def load_library(path: str = LIB_PATH):
     f32p, i64p, i32p = P(C.c_float), P(C.c_int64), P(C.c_int32)
     lib.suta_create.argtypes = [P(ModelConfigC), P(C.c_char_p), P(f32p), i64p, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_int64, P(C.c_void_p)]
+    lib.suta_create_family.argtypes = [P(ModelConfigC), P(ModelFamilyC)] + lib.suta_create.argtypes[1:]
     lib.suta_destroy.argtypes = [C.c_void_p]
     lib.suta_reset.argtypes = [C.c_void_p]
     lib.suta_num_frames.argtypes = [P(ModelConfigC), C.c_int64, i64p]
@@ -165,6 +170,11 @@ def config_to_c(cfg: dict) -> ModelConfigC:
     return m
 
 
+def family_to_c(cfg: dict) -> ModelFamilyC:
+    """suta_model_family of a geometry: `model_type` (absent = wav2vec2) and data2vec-audio's stack kernel size."""
+    return ModelFamilyC(FAMILY_ID[family(cfg)], int(cfg.get("conv_pos_kernel_size") or 0))
+
+
 def _ptr(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -184,8 +194,9 @@ class SutaEngine:
         cnum = (C.c_int64 * len(names))(*[a.size for a in arrs])
         self._c_cfg = config_to_c(cfg)
         h = C.c_void_p()
-        _check(self.lib.suta_create(C.byref(self._c_cfg), cnames, cdata, cnum, len(names), device, max_batch,
-                                    max_samples, C.byref(h)))
+        self._c_fam = family_to_c(cfg)
+        _check(self.lib.suta_create_family(C.byref(self._c_cfg), C.byref(self._c_fam), cnames, cdata, cnum, len(names),
+                                           device, max_batch, max_samples, C.byref(h)))
         self.handle = h
         self.max_batch = max_batch
         self.V = cfg["vocab_size"]

@@ -4,7 +4,14 @@ FLOPs_alg(N, S) = (S+1) * F(N) + S * B(N): the minimal schedule, 2 flops per MAC
 ops only (convs, linears, attention products).  Redundant re-forwards of the reference
 schedule are not credited.
 """
-from .config import adapter_dim, frame_lengths
+from .config import adapter_dim, family, frame_lengths
+
+
+def _pos_taps(cfg: dict) -> int:
+    """Taps of the positional embedding summed over its convs: wav2vec2 / HuBERT one conv of num_conv_pos_embeddings
+    taps, data2vec-audio num_conv_pos_embeddings convs of conv_pos_kernel_size taps."""
+    K = cfg["num_conv_pos_embeddings"]
+    return K * cfg["conv_pos_kernel_size"] if family(cfg) == "data2vec-audio" else K
 
 
 def forward_flops(cfg: dict, n_samples: int) -> float:
@@ -17,7 +24,7 @@ def forward_flops(cfg: dict, n_samples: int) -> float:
         cin = 1 if i == 0 else C[i - 1]
         conv += 2.0 * c * cin * k * L[i]
     proj = 2.0 * T * C[-1] * H
-    G, K = cfg["num_conv_pos_embedding_groups"], cfg["num_conv_pos_embeddings"]
+    G, K = cfg["num_conv_pos_embedding_groups"], _pos_taps(cfg)
     pos = 2.0 * T * (H // G) ** 2 * K * G
     lin = NL * T * (8.0 * H * H + 4.0 * H * F)
     att = NL * 4.0 * T * T * H
@@ -34,7 +41,7 @@ def backward_flops(cfg: dict, n_samples: int) -> float:
     head = 2.0 * T * H * V                           # dX only
     lin = NL * T * (8.0 * H * H + 4.0 * H * F)       # dX only (frozen weights)
     att = 2.0 * NL * 4.0 * T * T * H                 # dS, dQ, dK, dV
-    G, K = cfg["num_conv_pos_embedding_groups"], cfg["num_conv_pos_embeddings"]
+    G, K = cfg["num_conv_pos_embedding_groups"], _pos_taps(cfg)
     pos = 2.0 * T * (H // G) ** 2 * K * G            # dX only
     proj = 2.0 * (2.0 * T * C[-1] * H)               # dW + dX
     conv = 0.0

@@ -165,7 +165,10 @@ def workspace_bytes_per_audio_s(cfg, sdpl: bool = False, utt_s: float = 0.0) -> 
         attn = (cfg["num_hidden_layers"] + 1) * cfg["num_attention_heads"] * 50 * 50 * 4 * float(utt_s)
     from .config import adapter_dim
     per_frame = 14 + (1 if adapter_dim(cfg) else 0)   # attention adapters save their input h per layer (section 2)
-    return 50 * 4 * cfg["num_hidden_layers"] * per_frame * cfg["hidden_size"] + 6350 * 512 * 4 * 3 + head + attn
+    stack = 0.0
+    if cfg.get("model_type") == "data2vec-audio":   # z_j per layer of the positional stack + two ping-pong activations
+        stack = 50 * 4 * (cfg["num_conv_pos_embeddings"] + 2) * cfg["hidden_size"]
+    return 50 * 4 * cfg["num_hidden_layers"] * per_frame * cfg["hidden_size"] + 6350 * 512 * 4 * 3 + head + attn + stack
 
 
 def engine_fixed_bytes(cfg, weights, max_batch: int, precision: str = "fp32") -> float:

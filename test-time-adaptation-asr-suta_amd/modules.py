@@ -14,16 +14,20 @@ from __future__ import annotations
 
 from typing import List, Tuple
 
-from .config import adapter_dim
+from .config import adapter_dim, family, prefix
 
 # (name, is_layer_norm, own parameter names in registration order)
 Module = Tuple[str, bool, List[str]]
 
 
 def named_modules(cfg: dict) -> List[Module]:
-    """`Wav2Vec2ForCTC(cfg).named_modules()` in order (pre-order, registration order)."""
-    out: List[Module] = [("", False, []), ("wav2vec2", False, ["masked_spec_embed"])]
-    fe = "wav2vec2.feature_extractor"
+    """`Wav2Vec2ForCTC(cfg).named_modules()` in order (pre-order, registration order); for the hubert and
+    data2vec-audio families `HubertForCTC` / `Data2VecAudioForCTC`: the same tree under their own prefix, HuBERT's with
+    wav2vec2's module names throughout, data2vec's with one conv-layer class (conv, layer_norm, activation) and the
+    positional stack `pos_conv_embed.layers.J` (conv, padding, activation, an nn.LayerNorm without parameters)."""
+    base = prefix(cfg)[:-1]
+    out: List[Module] = [("", False, []), (base, False, ["masked_spec_embed"])]
+    fe = base + ".feature_extractor"
     out += [(fe, False, []), (fe + ".conv_layers", False, [])]
     group = cfg["feat_extract_norm"] == "group"
     conv_p = ["weight", "bias"] if cfg["conv_bias"] else ["weight"]
@@ -37,17 +41,25 @@ def named_modules(cfg: dict) -> List[Module]:
                 out += [(b + ".activation", False, [])]
         else:            # Wav2Vec2LayerNormConvLayer: conv, layer_norm (nn.LayerNorm), activation
             out += [(b + ".layer_norm", True, ["weight", "bias"]), (b + ".activation", False, [])]
-    fp = "wav2vec2.feature_projection"
+    fp = base + ".feature_projection"
     out += [(fp, False, []), (fp + ".layer_norm", True, ["weight", "bias"]),
             (fp + ".projection", False, ["weight", "bias"]), (fp + ".dropout", False, [])]
-    en = "wav2vec2.encoder"
+    en = base + ".encoder"
     pc = en + ".pos_conv_embed"
-    out += [(en, False, []), (pc, False, []), (pc + ".conv", False, ["bias"]),
-            (pc + ".conv.parametrizations", False, []),
-            (pc + ".conv.parametrizations.weight", False, ["original0", "original1"]),
-            (pc + ".conv.parametrizations.weight.0", False, []),
-            (pc + ".padding", False, []), (pc + ".activation", False, []),
-            (en + ".layer_norm", True, ["weight", "bias"]), (en + ".dropout", False, []),
+    out += [(en, False, []), (pc, False, [])]
+    if family(cfg) == "data2vec-audio":
+        out += [(pc + ".layers", False, [])]
+        for j in range(cfg["num_conv_pos_embeddings"]):
+            b = f"{pc}.layers.{j}"
+            out += [(b, False, []), (b + ".conv", False, ["weight", "bias"]), (b + ".padding", False, []),
+                    (b + ".activation", False, []), (b + ".layer_norm", True, [])]   # elementwise_affine=False
+    else:
+        out += [(pc + ".conv", False, ["bias"]),
+                (pc + ".conv.parametrizations", False, []),
+                (pc + ".conv.parametrizations.weight", False, ["original0", "original1"]),
+                (pc + ".conv.parametrizations.weight.0", False, []),
+                (pc + ".padding", False, []), (pc + ".activation", False, [])]
+    out += [(en + ".layer_norm", True, ["weight", "bias"]), (en + ".dropout", False, []),
             (en + ".layers", False, [])]
     for li in range(cfg["num_hidden_layers"]):
         lb = f"{en}.layers.{li}"

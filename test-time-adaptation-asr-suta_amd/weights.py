@@ -1,4 +1,4 @@
-"""Seeded synthetic Wav2Vec2ForCTC weights, and loading of local HF checkpoints.
+"""Seeded synthetic Wav2Vec2ForCTC (HubertForCTC, Data2VecAudioForCTC) weights, and loading of local HF checkpoints.
 
 Pretrained checkpoints are not reachable offline, so benches and
 parity tests run on weights drawn here.  Every tensor comes from its own
@@ -61,11 +61,12 @@ LEGACY_NAMES = (("weight_g", "parametrizations.weight.original0"),
 def remap_legacy(sd: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
     """Checkpoints saved before torch's parametrized weight_norm name the positional conv's
     weight-norm tensors `weight_g` / `weight_v`; HF maps them to `parametrizations.weight.original0/1`
-    on load.  Applied to every checkpoint format."""
-    for old, new in LEGACY_NAMES:
-        key = "wav2vec2.encoder.pos_conv_embed.conv." + old
-        if key in sd:
-            sd["wav2vec2.encoder.pos_conv_embed.conv." + new] = sd.pop(key)
+    on load (HubertForCTC's too, under `hubert.`).  Applied to every checkpoint format."""
+    for pfx in ("wav2vec2.", "hubert."):
+        for old, new in LEGACY_NAMES:
+            key = pfx + "encoder.pos_conv_embed.conv." + old
+            if key in sd:
+                sd[pfx + "encoder.pos_conv_embed.conv." + new] = sd.pop(key)
     return sd
 
 
