@@ -90,7 +90,7 @@ struct SutaSwitches {
                           // outputs are staged through LDS into whole-line stores; 1 = direct 16-B row-per-lane stores,
                           // 0 = the column-per-lane form shared with the 128 x 128 kernel
     int hbp_conv;         // SUTA_HBP_CONV (default 1): the conv stack's conv-seg input gradients on the four-phase 256 x 256
-                          // kernel (gemm.hip use_hbp_conv); 0 = the 128 x 128 kernel
+                          // kernel (gemm.hip hbx_conv_wins); 0 = the 128 x 128 kernel
     int hbt4;             // SUTA_HBT4 (default 1): the conv weight gradients (MN-contiguous bf16 planes) on the four-phase
                           // 256 x 256 kernel's TN form (gemm_hbp_kernel) on grids of >= 256 tiles; 2 on every grid
                           // (tests); 0 = gemm_hbt_kernel (128 x 128, two stages, split-K on small grids)
@@ -99,7 +99,7 @@ struct SutaSwitches {
     int loss_wide;        // SUTA_LOSS_WIDE (default 0): 1 = the any-vocabulary loss path (ops.hip loss_wide_*) also at
                           // vocab_size <= 64, where the one-block-per-utterance kernel runs by default (tests)
     int f32p;             // SUTA_F32P (default 1): the exact-fp32 GEMMs on the four-phase 256 x 256 kernel's fp32 forms
-                          // (gemm.hip use_f32p) on grids of >= 256 tiles; 2 = every eligible GEMM on any grid (tests);
+                          // (gemm.hip f32p_wins) on grids of >= 256 tiles; 2 = every eligible GEMM on any grid (tests);
                           // 0 = the 128 x 128 LDS-DMA kernel everywhere
     int sdpl_wide;        // SUTA_SDPL_WIDE (default 0): 1 = the any-vocabulary SDPL kernels (sdpl.hip sdpl_wide_*) also at
                           // vocab_size <= 32 under the 960h pseudo-label rule, where the 32-letter kernels run by
@@ -242,12 +242,52 @@ struct GemmParams {
 };
 
 void gemm_init(GemmParams& p);
-// whether gemm_launch(p) takes the 256 x 256 bf16-plane kernel with its C^T epilogue (the one that carries EPI_DELTA);
-// p as it will be launched (planes routed)
+
+// The kernel a GEMM takes (gemm.hip gemm_route): decided once per launch, from the params, the call's SutaSwitches
+// and the gemm_set_variant overrides.  The families' names are the census's kernel names.
+enum GemmFamily {
+    GF_F32,        // "f32":       register-staged fp32 MFMA (gemm_f32_kernel): operands the LDS-DMA loader cannot take
+    GF_GLDS,       // "glds":      LDS-DMA fp32 MFMA (gemm_glds_kernel), the exact-fp32 default
+    GF_X6,         // "x6":        fp32-accurate three-way bf16 split, six products (gemm_x6_kernel)
+    GF_X6_1PLANE,  // "x6_1plane": bf16 products from fp32 operands, register-staged (gemm_x6_kernel, one plane)
+    GF_GBF,        // "gbf":       the same on LDS-DMA fp32 stages (gemm_gbf_kernel): bf16 weight gradients
+    GF_GBF_X6,     // "gbf_x6":    x6 with register splits on LDS-DMA stages (benchmark variants only)
+    GF_HB,         // "hb":        k-contiguous bf16 planes, 128 x 128 family (gemm_hb_kernel)
+    GF_HBT,        // "hbt":       MN-contiguous bf16 planes, 128 x 128 (gemm_hbt_kernel)
+    GF_HBT4,       // "hbt4":      MN-contiguous bf16 planes on the four-phase 256 x 256 kernel's TN form
+    GF_HBX,        // "hbx":       k-contiguous bf16 planes on the 256 x 256 kernels, 32x32x16 / four-phase forms
+    GF_HBX16,      // "hbx16":     the slice-ring 256 x 256 kernel on 16x16x32 MFMAs (benchmark variant only)
+    GF_F32P,       // "f32p":      exact fp32 on the four-phase 256 x 256 kernel's fp32 forms
+};
+const char* gemm_family_name(GemmFamily f);
+
+struct GemmRoute {
+    GemmFamily family;
+    int BM, BN;      // block tile
+    int stages, bk;  // f32 / glds / x6 / gbf / hb: LDS stages and K-step (operand elements) of the instantiation
+    // the 256 x 256 families (hbx, hbx16, hbt4, f32p; gemm_hbx.hip):
+    bool four_phase;  // gemm_hbp_kernel (else gemm_hbx_kernel, the slice ring)
+    int form;         // gemm_hbp_kernel's main loop, 1..4 (SUTA_HBX_FORM)
+    int ct;           // epilogue: 0 column per lane, 1 C^T accumulators with direct row stores, 2 C^T staged through LDS
+    bool conv, tn;    // gemm_hbp_kernel's CONV (conv-A rows, weight segments) and TN (MN-contiguous planes) forms
+    int f32;          // gemm_hbp_kernel's fp32 form: 0 bf16 planes, 1 A and B k-contiguous, 2 B row-contiguous
+    int em;           // epilogue class: the flags the instantiation carries (-1: all)
+    int dbg;          // tools build only (-DSUTA_HBX_DIAG): the kernel's diagnostic form, 0 in libsuta.so
+    // launch shape: the values gemm_launch writes into GemmParams' internal fields, and the grid
+    int splits, kchunk, order, off32, fgelu, va, vb;
+    unsigned gx, gy, gz;
+};
+// Validates p (std::invalid_argument) and chooses its kernel.  Pure: reads p, the latched switches and the
+// gemm_set_variant overrides.  have_ws / ws_floats: the split-K workspace gemm_launch will be given.
+GemmRoute gemm_route(const GemmParams& p, bool have_ws, long ws_floats);
+// whether the route is the 256 x 256 bf16-plane kernel with a C^T epilogue (the one that carries EPI_DELTA)
+inline bool gemm_route_hbx_t(const GemmRoute& r) { return r.family == GF_HBX && r.ct > 0; }
+// the same question of gemm_launch(p); p as it will be launched (planes routed)
 bool gemm_hbx_t_selected(const GemmParams& p);
 // Launch; ws/ws_floats: scratch for split-K (may be null -> no split).
 void gemm_launch(GemmParams p, hipStream_t st, float* ws, long ws_floats);
-// Benchmark/test override: tile (-1 auto, 0 128x128, 1 128x64, 2 64x128, 3 64x64), LDS buffers (1|2).
+// Benchmark/test override: tile (-1 auto, 0 128x128, 1 128x64, 2 64x128, 3 64x64, 4 256x128, 5 128x256, 8 / 9 the
+// 256 x 256 bf16-plane kernel on 32x32x16 / 16x16x32 MFMAs), nbuf: the family's stage variant (gemm.hip forced_*).
 void gemm_set_variant(int tile, int nbuf);
 // 0 = exact fp32 MFMA (v_mfma_f32_32x32x2_f32); 1 = fp32-accurate 3-way bf16 split (6 bf16 MFMA products);
 // 2 = bf16 GEMM (operands rounded to bf16 once, one bf16 MFMA product, fp32 accumulate).

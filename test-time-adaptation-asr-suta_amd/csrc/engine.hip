@@ -638,62 +638,60 @@ struct suta_engine {
         gemm(g);
     }
     void build_weight_planes();
+    // Where the bf16 planes of a GEMM's operands come from.  resolve_planes() sets the engine's precision mode in p
+    // and routes the frozen weight's plane; it changes nothing else and launches nothing.
+    enum Planes {
+        CALLER_PLANES,   // both planes given by the caller (conv stack)
+        PRODUCER_PLANE,  // linear with a frozen weight: the weight's plane, and A's plane written by A's producer
+        CONVERT_A,       // the same, but A's plane is yet to be converted from the fp32 A (gemm() does, into abuf)
+        PLANELESS,       // fp32 operands (a plane given for a non-frozen B is ignored)
+    };
+    Planes resolve_planes(GemmParams& p) {
+        p.mode = gemm_mode;
+        if (bf16_mode() && p.Ab && p.Bb) return CALLER_PLANES;
+        if (bf16_mode() && p.segK == 0 && !p.ta && p.Z == 1 && p.K % 8 == 0 && p.lda % 4 == 0 &&
+            (reinterpret_cast<uintptr_t>(p.A) & 15) == 0) {
+            auto it = wplanes.find(p.B);
+            if (it != wplanes.end() && (p.tb ? p.ldb == p.K : p.ldb == p.N)) {
+                p.Bb = p.tb ? it->second.first : it->second.second;
+                p.ldbb = p.K;
+                return p.Ab ? PRODUCER_PLANE : CONVERT_A;
+            }
+        }
+        p.Ab = nullptr;
+        return PLANELESS;
+    }
     // whether gemm(p0) takes the 256 x 256 bf16-plane kernel's C^T epilogue (the producer's A plane given, B a frozen
     // weight with planes): the condition for fusing EPI_DELTA into it
     bool routes_to_hbx_t(const GemmParams& p0) {
-        if (!bf16_mode() || !p0.Ab || p0.segK != 0 || p0.ta || p0.Z != 1 || p0.K % 8) return false;
-        auto it = wplanes.find(p0.B);
-        if (it == wplanes.end() || !(p0.tb ? p0.ldb == p0.K : p0.ldb == p0.N)) return false;
         GemmParams p = p0;
-        p.mode = gemm_mode;
-        p.Bb = p.tb ? it->second.first : it->second.second;
-        p.ldbb = p.K;
-        return gemm_hbx_t_selected(p);
+        return p.Ab && resolve_planes(p) == PRODUCER_PLANE && gemm_hbx_t_selected(p);
     }
     void gemm(const GemmParams& p0) {
         GemmParams p = p0;
-        p.mode = gemm_mode;
+        const Planes planes = resolve_planes(p);
         gemm_shape.clear();
         if (timing && gemm_census_is_on()) {  // per-shape time table (census + timing: tools/gemm_shapes.py)
             char key[200];
             snprintf(key, sizeof key, "M=%d N=%d K=%d z=%d %s%s epi=%d%s%s%s%s", p.M, p.N, p.K, p.Z, p.ta ? "T" : "N",
-                     p.tb ? "T" : "N", p.epi, p.segK > 0 ? " conv" : "", p.Ab ? " Ab" : "", p.C ? " C" : "",
+                     p.tb ? "T" : "N", p.epi, p.segK > 0 ? " conv" : "", p0.Ab ? " Ab" : "", p.C ? " C" : "",
                      p.Cb ? " Cb" : "");
             gemm_shape = key;
         }
-        if (bf16_mode() && p.Ab && p.Bb) {  // both planes given by the caller (conv stack)
-            timed(F_GEMM, [&] { gemm_launch(p, st, plan.splitws, plan.splitws_floats); }, timing ? gemm_alg_bytes(p) : 0.0);
-            return;
+        if (planes == CONVERT_A) {
+            if (!p.A) throw SutaError(SUTA_ERR_UNSUPPORTED, "gemm: neither an fp32 A nor its bf16 plane");
+            if (abuf.alloc((size_t)p.M * p.K * 2 + 256)) drop_graph();
+            p.Ab = abuf.p;
+            p.ldab = p.K;
+        } else if (planes == PLANELESS) {
+            if (!p.C) throw SutaError(SUTA_ERR_UNSUPPORTED, "gemm: fp32 output skipped on a plane-less GEMM");
+            if (!p.A) throw SutaError(SUTA_ERR_UNSUPPORTED, "gemm: fp32 A not written (bf16-plane producer) on a plane-less GEMM");
+            if (p.Cb) throw SutaError(SUTA_ERR_UNSUPPORTED, "gemm: a bf16 C plane (read by the next kernel) requested on a plane-less GEMM");
         }
-        if (bf16_mode() && p.segK == 0 && !p.ta && p.Z == 1 && p.K % 8 == 0 && p.lda % 4 == 0 &&
-            (reinterpret_cast<uintptr_t>(p.A) & 15) == 0) {
-            auto it = wplanes.find(p.B);
-            const bool fits = it != wplanes.end() && (p.tb ? p.ldb == p.K : p.ldb == p.N);
-            if (fits) {  // linear with a frozen weight: the bf16-plane GEMM
-                p.Bb = p.tb ? it->second.first : it->second.second;
-                p.ldbb = p.K;
-                if (p.Ab) {  // the producer of A wrote its bf16 plane
-                    timed(F_GEMM, [&] { gemm_launch(p, st, plan.splitws, plan.splitws_floats); },
-                          timing ? gemm_alg_bytes(p) : 0.0);
-                    return;
-                }
-                if (!p.A) throw SutaError(SUTA_ERR_UNSUPPORTED, "gemm: neither an fp32 A nor its bf16 plane");
-                if (abuf.alloc((size_t)p.M * p.K * 2 + 256)) drop_graph();
-                p.Ab = abuf.p;
-                p.ldab = p.K;
-                timed(F_GEMM, [&] {
-                    launch_to_bf16(p.A, p.lda, p.M, p.K, abuf.p, st);
-                    gemm_launch(p, st, plan.splitws, plan.splitws_floats);
-                }, timing ? gemm_alg_bytes(p, true) : 0.0);
-                return;
-            }
-        }
-        if (!p.C) throw SutaError(SUTA_ERR_UNSUPPORTED, "gemm: fp32 output skipped on a plane-less GEMM");
-        if (!p.A) throw SutaError(SUTA_ERR_UNSUPPORTED, "gemm: fp32 A not written (bf16-plane producer) on a plane-less GEMM");
-        if (p.Cb) throw SutaError(SUTA_ERR_UNSUPPORTED, "gemm: a bf16 C plane (read by the next kernel) requested on a plane-less GEMM");
-        p.Ab = nullptr;  // (plane-less GEMM: a plane given for a non-frozen B is ignored)
-        p.Cb = nullptr;
-        timed(F_GEMM, [&] { gemm_launch(p, st, plan.splitws, plan.splitws_floats); }, timing ? gemm_alg_bytes(p) : 0.0);
+        timed(F_GEMM, [&] {
+            if (planes == CONVERT_A) launch_to_bf16(p.A, p.lda, p.M, p.K, abuf.p, st);
+            gemm_launch(p, st, plan.splitws, plan.splitws_floats);
+        }, timing ? gemm_alg_bytes(p, planes == CONVERT_A) : 0.0);
     }
 
     // one GEMM per utterance (trainable per-slot weights, conv layers): operands by utt()

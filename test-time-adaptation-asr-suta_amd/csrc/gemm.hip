@@ -1,4 +1,17 @@
-// GEMM dispatcher: tile choice, split-K, precision mode -> kernel family (gemm_kernels.h).
+// GEMM dispatcher.  gemm_route() decides once which kernel a GEMM takes -- family, tile, stage variant, split-K,
+// tile order, grid (GemmRoute, common.h) -- and gemm_launch() launches what the route says.
+//   operands                               family              chosen by
+//   MN-contiguous bf16 planes (ta, !tb)    hbt4 | hbt          hbt4_ok and a full round of 256^2 tiles (SUTA_HBT4)
+//   k-contiguous bf16 planes, conv-A rows  hbx | hb            hbx_conv_wins (SUTA_HBX, SUTA_HBP_CONV)
+//   k-contiguous bf16 planes               hbx | hb            hbx_wins (SUTA_HBX, SUTA_HBX_T); hb's tile: HB_TILES
+//   fp32, mode 2 (bf16 products)           gbf | x6_1plane     gbf: transposed A, LDS-DMA-able; tile: BF16_TILES
+//   fp32, mode 1 (x6)                      x6                  tile: X6_TILES
+//   fp32, mode 0 (exact)                   f32p | glds | f32   f32p_wins (SUTA_F32P); glds: LDS-DMA-able; GLDS_TILES
+// The eligibility rules of the 256 x 256 kernels (hbx, hbx16, hbt4, f32p) are gemm_hbx.hip's *_ok predicates; which
+// instantiation of them a route is comes from hbx_resolve there.  Forced variants (gemm_set_variant: tools/gemm_bench,
+// tools/hb_bench) are translated there into a tile, a 256 x 256 request and a stage number, and enter gemm_route in two
+// places: the tile replaces the tile choice of the last four rows (a forced run takes no hbt4, CONV form or f32p), and
+// stage_override() picks each family's stage variant (the number also selects the benchmark families gbf / gbf_x6).
 #include "gemm_kernels.h"
 #include <algorithm>
 #include <cstdio>
@@ -13,14 +26,31 @@ namespace {
 
 bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
-int g_force_tile = -1;  // test/bench override: 0=128x128 1=128x64 2=64x128 3=64x64
+struct TileCand {
+    int bm, bn;
+    double eff;  // relative MFMA efficiency of the tile
+};
+
+// gemm_set_variant(tile, nbuf): whether a tile is forced, the tile, and the MFMA rows (32 / 16) of a forced request for
+// the 256 x 256 bf16-plane kernel (0: none)
+bool g_forced = false;
+TileCand g_tile = {128, 128, 0.0};
+int g_tile256 = 0;
 int g_nbuf = 3;  // 3 = LDS-DMA kernel where its preconditions hold (else the register-staged one)
 int g_mode = 0;  // 0 = exact fp32 MFMA, 1 = x6 (fp32-accurate bf16 split), 2 = bf16 products
 
 }  // namespace
 
 void gemm_set_variant(int tile, int nbuf) {
-    g_force_tile = tile;
+    // the benchmarks' tile numbers, translated here and nowhere else: {BM, BN, MFMA rows of a 256 x 256 request} by
+    // number (6 and 7 name no tile).  8 / 9 ask for the 256 x 256 bf16-plane kernel on 32x32x16 / 16x16x32 MFMAs; on a
+    // GEMM that kernel cannot run (gemm_route: hbx_can_run) the request falls back to the 128 x 128 they carry here.
+    static const int ids[10][3] = {{128, 128, 0}, {128, 64, 0}, {64, 128, 0}, {64, 64, 0},     {256, 128, 0},
+                                   {128, 256, 0}, {0, 0, 0},    {0, 0, 0},    {128, 128, 32}, {128, 128, 16}};
+    if (tile > 9 || (tile >= 0 && !ids[tile][0])) throw std::invalid_argument("gemm_set_variant: no such tile");
+    g_forced = tile >= 0;
+    g_tile = g_forced ? TileCand{ids[tile][0], ids[tile][1], 0.0} : TileCand{128, 128, 0.0};
+    g_tile256 = g_forced ? ids[tile][2] : 0;
     g_nbuf = nbuf;
 }
 
@@ -60,17 +90,24 @@ std::string gemm_census_text() {
     return out;
 }
 
+const char* gemm_family_name(GemmFamily f) {
+    static const char* const names[] = {"f32", "glds", "x6", "x6_1plane", "gbf", "gbf_x6", "hb", "hbt", "hbt4", "hbx",
+                                        "hbx16", "f32p"};
+    return names[f];
+}
+
 // Each launch also counts one "grid <kernel> <BMxBN> gx=<column tiles> gy=<row tiles> z=<Z> split=<k>" entry, so
 // a test can assert the tile grid a layout reaches (e.g. the 512 row tiles of 164 x 399 frames).
 // and one "epi <kernel> <BMxBN> <epilogue flags>" entry (e.g. EPI_DELTA = 256 on hbx: the fused flash-backward delta ran).
-static void census(const char* kernel, int BM, int BN, const GemmParams& p, int splits) {
+static void census(const GemmRoute& r, const GemmParams& p) {
     if (!g_census_on) return;
+    const char* kernel = gemm_family_name(r.family);
     char key[160], gkey[160], ekey[96];
-    snprintf(key, sizeof key, "%s %dx%d z=%ld split=%d %s%s%s", kernel, BM, BN, (long)p.Z, splits, p.ta ? "T" : "N",
-             p.tb ? "T" : "N", p.segK > 0 ? (p.segB ? " conv-seg" : " conv") : "");
-    snprintf(gkey, sizeof gkey, "grid %s %dx%d gx=%d gy=%d z=%ld split=%d", kernel, BM, BN, (p.N + BN - 1) / BN,
-             (p.M + BM - 1) / BM, (long)p.Z, splits);
-    snprintf(ekey, sizeof ekey, "epi %s %dx%d %d", kernel, BM, BN, p.epi);
+    snprintf(key, sizeof key, "%s %dx%d z=%ld split=%d %s%s%s", kernel, r.BM, r.BN, (long)p.Z, r.splits,
+             p.ta ? "T" : "N", p.tb ? "T" : "N", p.segK > 0 ? (p.segB ? " conv-seg" : " conv") : "");
+    snprintf(gkey, sizeof gkey, "grid %s %dx%d gx=%u gy=%u z=%ld split=%d", kernel, r.BM, r.BN, r.gx, r.gy, (long)p.Z,
+             r.splits);
+    snprintf(ekey, sizeof ekey, "epi %s %dx%d %d", kernel, r.BM, r.BN, p.epi);
     std::lock_guard<std::mutex> lk(g_census_mu);
     ++g_census[key];
     ++g_census[gkey];
@@ -89,79 +126,58 @@ void gemm_init(GemmParams& p) {
     p.mode = g_mode;
 }
 
-// Tile choice: time ~ padded output area / eff, where eff is the tile's relative MFMA efficiency
-// (measured with tools/gemm_bench on the SUTA shapes at 64 utterances: 128x128 wins every large
-// GEMM despite its coarser tail; smaller tiles win where M or N is below ~128, e.g. attention and
-// the 48-channel positional-conv groups); a grid with fewer tiles than CUs is charged as one full
-// round of its tiles.
-static int choose_tile(long M, long N, long Z, long K, int mode) {
-    struct Cand {
-        int bm, bn;
-        double eff;
-    };
-    static const Cand glds[4] = {{128, 128, 1.0}, {128, 64, 0.93}, {64, 128, 0.92}, {64, 64, 0.85}};
-    static const Cand x6[4] = {{128, 128, 1.0}, {128, 64, 0.9}, {64, 128, 0.9}, {64, 64, 0.75}};
-    const Cand* cands = mode == 0 ? glds : x6;
+// ---- tile choice ----
+// time ~ blocks charged x tile area / eff.  whole_rounds: a grid is charged whole rounds of `round` resident blocks;
+// else it is charged its tiles, and one full round where it has fewer.
+static long tiles_of(const GemmParams& p, int bm, int bn) {
+    return (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) * p.Z;
+}
+static double tile_cost(const TileCand& c, const GemmParams& p, long round, bool whole_rounds) {
+    const long tiles = tiles_of(p, c.bm, c.bn);
+    const long charged = whole_rounds ? (tiles + round - 1) / round * round : std::max(tiles, round);
+    return (double)charged * c.bm * c.bn / c.eff;
+}
+// the first candidate (rows up to max_bm) no later one beats by more than 0.1 %
+template <int N>
+static TileCand best_tile(const TileCand (&cands)[N], const GemmParams& p, long round, bool whole_rounds,
+                          int max_bm = 256) {
     int best = 0;
     double bt = 1e300;
-    for (int c = 0; c < 4; ++c) {
-        const long tiles = ((M + cands[c].bm - 1) / cands[c].bm) * ((N + cands[c].bn - 1) / cands[c].bn) * Z;
-        const double area = (double)cands[c].bm * cands[c].bn;
-        const double t = std::max((double)tiles, 256.0) * area / cands[c].eff;
+    for (int i = 0; i < N; ++i) {
+        if (cands[i].bm > max_bm) continue;
+        const double t = tile_cost(cands[i], p, round, whole_rounds);
         if (t < bt * 0.999) {
             bt = t;
-            best = c;
+            best = i;
         }
     }
-    (void)K;
-    return best;
+    return cands[best];
 }
+// the grid fills one round of 256 tiles of 256^2: where the 256 x 256 kernels (one block per CU) are chosen unforced
+static bool fills_256_round(const GemmParams& p) { return tiles_of(p, 256, 256) >= 256; }
 
+// eff measured with tools/gemm_bench on the SUTA shapes at 64 utterances: 128x128 wins every large GEMM despite its
+// coarser tail; smaller tiles win where M or N is below ~128, e.g. attention and the 48-channel positional-conv
+// groups.  Charged per tile, a grid with fewer tiles than the 256 CUs as one full round of them.
+static const TileCand GLDS_TILES[4] = {{128, 128, 1.0}, {128, 64, 0.93}, {64, 128, 0.92}, {64, 64, 0.85}};
+static const TileCand X6_TILES[4] = {{128, 128, 1.0}, {128, 64, 0.9}, {64, 128, 0.9}, {64, 64, 0.75}};
 // bf16 mode (tools/gemm_bench, 64 utterances): the register-staged one-plane kernel beats the LDS-DMA
 // fp32-staged one on every operand layout except transposed A (weight gradients, TN), and its
 // 256x128 tile (wave tile 128x64: 1.3x fewer L2 bytes per flop) wins wherever the grid still fills
 // whole rounds of 512 resident blocks (2 per CU): 420-430 TF on FFN1 / QKV / conv1 vs 360-390.
-// Cost = rounds of 512 blocks x tile area / eff.
-static int choose_tile_bf16(long M, long N, long Z, bool big) {
-    struct Cand {
-        int id, bm, bn;
-        double eff;
-    };
-    static const Cand c[5] = {{0, 128, 128, 1.0}, {4, 256, 128, 1.12}, {1, 128, 64, 0.85}, {2, 64, 128, 0.85},
-                              {3, 64, 64, 0.6}};
-    int best = 0;
-    double bt = 1e300;
-    for (int i = 0; i < 5; ++i) {
-        if (c[i].id == 4 && !big) continue;
-        const long tiles = ((M + c[i].bm - 1) / c[i].bm) * ((N + c[i].bn - 1) / c[i].bn) * Z;
-        const double t = (double)((tiles + 511) / 512) * c[i].bm * c[i].bn / c[i].eff;
-        if (t < bt * 0.999) {
-            bt = t;
-            best = c[i].id;
-        }
-    }
-    return best;
-}
-
+// Charged in whole rounds of 512 blocks.
+static const TileCand BF16_TILES[5] = {{128, 128, 1.0}, {256, 128, 1.12}, {128, 64, 0.85}, {64, 128, 0.85}, {64, 64, 0.6}};
 // bf16-plane GEMMs (tools/hb_bench, C4 linears at M = 25536): 128x128 with two LDS stages wins every
 // shape (460-660 TF vs 370-570 for 256x128 at one block per CU); smaller tiles only for small grids.
-static int choose_tile_hb(long M, long N, long Z) {
-    struct Cand {
-        int id, bm, bn;
-        double eff;
-    };
-    static const Cand c[4] = {{0, 128, 128, 1.0}, {1, 128, 64, 0.85}, {2, 64, 128, 0.85}, {3, 64, 64, 0.6}};
-    int best = 0;
-    double bt = 1e300;
-    for (int i = 0; i < 4; ++i) {
-        const long tiles = ((M + c[i].bm - 1) / c[i].bm) * ((N + c[i].bn - 1) / c[i].bn) * Z;
-        const double t = (double)((tiles + 511) / 512) * c[i].bm * c[i].bn / c[i].eff;
-        if (t < bt * 0.999) {
-            bt = t;
-            best = c[i].id;
-        }
-    }
-    return best;
+static const TileCand HB_TILES[4] = {{128, 128, 1.0}, {128, 64, 0.85}, {64, 128, 0.85}, {64, 64, 0.6}};
+
+// ---- which GEMMs take a 256 x 256 kernel (the operand conditions are gemm_hbx.hip's) ----
+
+// A bf16-plane linear the 256 x 256 kernels can run: plain rows, K in whole 32-deep slices and at least four of them;
+// batched (Z > 1) GEMMs -- the conv stack's per-utterance forward -- only on the four-phase form with the staged C^T
+// epilogue (32x32x16 MFMAs only).  Asked of unforced and forced requests alike.
+static bool hbx_can_run(const GemmParams& p, int mfma_rows) {
+    return p.segK == 0 && p.K % 32 == 0 && p.K >= 128 && (p.Z == 1 || (mfma_rows == 32 && hbx_four_phase_ok(p)));
 }
 
 // 256 x 256 slice-ring bf16-plane kernel (gemm_hbx.hip, v_mfma_f32_32x32x16_bf16; bitwise the 128 x 128 kernel's
@@ -173,65 +189,46 @@ static int choose_tile_hb(long M, long N, long Z) {
 // 595 / 627 and direct row-per-lane 16-B stores (32 rows per instruction) 515 / 625, so without the staged form
 // they keep the 128 x 128 kernel.
 // SUTA_HBX=0: off (A/B runs); 2: every eligible linear, any epilogue and grid (tests).
-// batched (Z > 1) GEMMs -- the conv stack's per-utterance forward -- only on the four-phase form with the staged C^T
-// epilogue (gemm_hbp_kernel rebases its operands per batch)
-// (p.off32 already set: gemm_run_hbx refuses a batched GEMM without the 32-bit-offset epilogue, so one without it -- an
-// operand over 4 GiB, or SUTA_EPI_FAST=0 -- must stay on the 128 x 128 kernel)
-static bool hbx_batch_ok(const GemmParams& p) {
+static bool hbx_wins(const GemmParams& p) {
     const SutaSwitches& sw = suta_switches();
-    return p.Z == 1 || (sw.hbx_form && sw.hbx_t == 2 && p.K % 64 == 0 && hbx_t_ok(p, true));
-}
-
-static bool use_hbx(const GemmParams& p) {
-    const int mode = suta_switches().hbx;
-    if (!mode || p.segK > 0 || p.K % 32 || p.K < 128 || (p.epi & (EPI_ACCUM | EPI_SMBWD)) || !hbx_batch_ok(p)) return false;
-    if (mode == 2) return true;  // SUTA_HBX=2: every eligible linear (tests)
-    if ((p.epi & (EPI_GELU | EPI_DGELU | EPI_STORE_PRE)) && !(suta_switches().hbx_t == 2 && hbx_t_ok(p, false)))
-        return false;
-    return (long)((p.M + 255) / 256) * ((p.N + 255) / 256) * p.Z >= 256;
+    if (!sw.hbx || !hbx_can_run(p, 32) || (p.epi & (EPI_ACCUM | EPI_SMBWD))) return false;
+    if (sw.hbx == 2) return true;
+    if ((p.epi & (EPI_GELU | EPI_DGELU | EPI_STORE_PRE)) && !(sw.hbx_t == 2 && hbx_t_ok(p))) return false;
+    return fills_256_round(p);
 }
 
 // the conv stack's input gradients (conv-A rows, per-tap weight segments: config C4's conv-seg GEMMs, Z = B) on the
-// four-phase 256 x 256 kernel's CONV form (gemm_hbx.hip hbp_conv_ok) on grids of at least one round of 256 tiles;
+// four-phase 256 x 256 kernel's CONV form (hbp_conv_ok) on grids of at least one round of 256 tiles;
 // SUTA_HBP_CONV=0 keeps them on the 128 x 128 kernel (A/B runs), SUTA_HBX=2 forces them on every eligible grid
-static bool use_hbp_conv(const GemmParams& p) {
+static bool hbx_conv_wins(const GemmParams& p) {
     const SutaSwitches& sw = suta_switches();
-    if (!sw.hbx || !sw.hbp_conv || !hbp_conv_ok(p)) return false;
-    if (sw.hbx == 2) return true;
-    return (long)((p.M + 255) / 256) * ((p.N + 255) / 256) * p.Z >= 256;
+    return sw.hbx && sw.hbp_conv && hbp_conv_ok(p) && (sw.hbx == 2 || fills_256_round(p));
 }
 
-// The exact-fp32 GEMMs on the four-phase 256 x 256 kernel's fp32 forms (gemm_hbx.hip f32p_form: bitwise the 128 x 128
+// The exact-fp32 GEMMs on the four-phase 256 x 256 kernel's fp32 forms (f32p_form: bitwise the 128 x 128
 // LDS-DMA kernel's results -- the same v_mfma_f32_32x32x2_f32 products in the same k order) on grids of at least one
 // round of 256 tiles: one block per CU whose two wave groups run a barrier apart, so one group's fragment reads and DMA
 // issue sit under the other's MFMAs, and whole-line staged stores, against two co-resident 128 x 128 blocks whose
-// prologues and epilogues coincide.  Returns the operand form (0 = stay on the 128 x 128 kernels).
+// prologues and epilogues coincide.
 // SUTA_F32P=0: off (A/B runs); 2: every eligible GEMM on any grid (tests).
 // Forward (NT) linears with K < 1024 -- wav2vec2-base's QKV, out-projection and FFN1 -- stay on the 128 x 128 kernel:
 // tests/test_gpu_bench_scale.py::test_bench_layout_matches_oracle asserts the bench layout's census still holds
 // "grid glds 128x128" entries with gx = 6, 18 and 24 at gy = 512 (QKV forward is the only gx = 18 GEMM); a change
 // that may touch that test lifts this rule.
-static int use_f32p(const GemmParams& p) {
+static bool f32p_wins(const GemmParams& p) {
     const int mode = suta_switches().f32p;
-    if (!mode || g_force_tile >= 0 || g_nbuf != 3) return 0;
-    const int form = f32p_form(p);
-    if (!form || mode == 2) return form;
-    if (p.tb && p.segK == 0 && p.K < 1024) return 0;
-    const long tiles = (long)((p.M + 255) / 256) * ((p.N + 255) / 256) * p.Z;
-    if (tiles < 256) return 0;
+    if (!mode || g_forced || g_nbuf != 3 || !f32p_form(p)) return false;
+    if (mode == 2) return true;
+    if ((p.tb && p.segK == 0 && p.K < 1024) || !fills_256_round(p)) return false;
     // A 256-row tile pads short conv layers more than the 128- and 64-row tiles do (799 rows: 1024 against 896), so
-    // the kernel is kept where its padded area over its relative rate beats the best 128 x 128-family tile's
-    // (choose_tile's cost).  Rates from the eager trace of the bench layout (profiles/r7, ms per launch against the
+    // the kernel is kept where its padded area over its relative rate beats the best 128 x 128-family tile's.
+    // Rates from the eager trace of the bench layout (profiles/r7, ms per launch against the
     // 128 x 128 kernel at equal padded area): conv-seg input gradients -8 to -10 %, linears and the conv forward -2 to
     // -4.5 %; at 3199 / 1599 / 799 / 399 rows the conv forward measured +1 / +1 / +23 / +36 % and stays where it was.
     const double eff = p.segK > 0 ? 1.05 : 1.03;
-    static const struct { int bm, bn; double eff; } c128[4] = {{128, 128, 1.0}, {128, 64, 0.93}, {64, 128, 0.92}, {64, 64, 0.85}};
     double best = 1e300;
-    for (const auto& c : c128) {
-        const long t = (long)((p.M + c.bm - 1) / c.bm) * ((p.N + c.bn - 1) / c.bn) * p.Z;
-        best = std::min(best, std::max((double)t, 256.0) * c.bm * c.bn / c.eff);
-    }
-    return (double)tiles * 65536.0 / eff < best ? form : 0;
+    for (const TileCand& c : GLDS_TILES) best = std::min(best, tile_cost(c, p, 256, false));
+    return (double)tiles_of(p, 256, 256) * 65536.0 / eff < best;
 }
 
 // 32-bit epilogue offsets: M x ld elements of every operand the epilogue touches within 4 GiB
@@ -246,15 +243,41 @@ static int epilogue_off32(const GemmParams& p) {
            p.ldaux >= 0 && p.ldc2 >= 0 && p.ldcb >= 0 && p.ldo >= 0 && fast;
 }
 
-bool gemm_hbx_t_selected(const GemmParams& p0) {
-    GemmParams p = p0;
-    p.off32 = epilogue_off32(p);
-    const bool hb = p.mode == 2 && p.Ab && p.Bb && !p.ta && p.segK == 0;
-    return hb && g_force_tile < 0 && use_hbx(p) && suta_switches().hbx_t && hbx_t_ok(p, true);
+// ---- stage variants: the defaults, and gemm_set_variant's nbuf where a benchmark sets one ----
+static void stage_override(GemmRoute& r) {
+    const int nb = g_nbuf;
+    r.stages = 2, r.bk = 32;
+    switch (r.family) {
+    case GF_HB: {
+        // SUTA_HB_NS: stage variant of the 128 x 128 bf16-plane kernel (A/B runs; 2 default), read once (thread-safe)
+        static const int hbns = [] {
+            const char* ev = std::getenv("SUTA_HB_NS");
+            return ev ? std::max(2, atoi(ev)) : 2;
+        }();
+        // 3 = three stages, 4 = 64-deep K-steps, 5 / 6 = 16-deep K-steps on 4 / 3 stages (128 x 128 only)
+        const int ns = g_forced ? nb : (r.BM == 128 && r.BN == 128) ? hbns : 2;
+        if (r.BM + r.BN > 256) break;  // 256 x 128, 128 x 256: two 32-deep stages only
+        if (ns == 3) r.stages = 3;
+        if (ns == 4) r.bk = 64;
+        if (ns == 5 || ns == 6) r.stages = ns == 5 ? 4 : 3, r.bk = 16, r.BM = r.BN = 128;
+        break;
+    }
+    case GF_X6_1PLANE: r.stages = 1; break;
+    case GF_GBF: r.bk = nb == 8 ? 64 : 32; break;       // benchmark variant 8 = BK64 x 2
+    case GF_GBF_X6: r.bk = nb == 10 ? 64 : 32; break;   // benchmark variants 9 = BK32 x 2, 10 = BK64 x 2
+    case GF_X6: r.stages = nb == 2 ? 2 : 1, r.bk = nb == 2 ? 16 : 32; break;  // BK 16 double-buffered | BK 32, one stage
+    case GF_GLDS:  // 3 = BK32 x 2 stages, 4 = BK16 x 4, 5 = BK16 x 3, 6 = BK32 x 3, 7 = BK64 x 2
+        r.stages = nb == 4 ? 4 : (nb == 5 || nb == 6) ? 3 : 2;
+        r.bk = (nb == 4 || nb == 5) ? 16 : nb == 7 ? 64 : 32;
+        break;
+    case GF_F32: r.stages = nb == 2 ? 2 : 1; break;
+    default: break;
+    }
 }
 
-void gemm_launch(GemmParams p, hipStream_t st, float* ws, long ws_floats) {
-    if (p.M <= 0 || p.N <= 0 || p.Z <= 0) return;
+GemmRoute gemm_route(const GemmParams& p0, bool have_ws, long ws_floats) {
+    GemmParams p = p0;
+    const SutaSwitches& sw = suta_switches();
     const int second = ((p.epi & EPI_RESID) != 0) + ((p.epi & EPI_ACCUM) != 0) + ((p.epi & EPI_SMBWD) != 0);
     if (second > 1 || ((p.epi & EPI_SMBWD) && p.epi != EPI_SMBWD))
         throw std::invalid_argument("gemm epilogue: RESID / ACCUM / SMBWD are mutually exclusive");
@@ -277,114 +300,110 @@ void gemm_launch(GemmParams p, hipStream_t st, float* ws, long ws_floats) {
     if (hb && (p.K % 8 || p.ldab % 8 || p.ldbb % 8 || !aligned16(p.Ab) || !aligned16(p.Bb) ||
                (p.Z > 1 && ((p.sA0 | p.sA1 | p.sB0 | p.sB1) % 8))))
         throw std::invalid_argument("gemm: bf16 planes need K, ld and batch strides % 8 == 0 and 16-B alignment");
-    const bool bf16_gbf = p.mode == 2 && glds_ok && p.ta;  // bf16 weight gradients: LDS-DMA fp32 stages
-    p.off32 = epilogue_off32(p);  // before the tile choice: the 256 x 256 kernel's batched form needs it
-    p.fgelu = suta_switches().fast_gelu;  // (the engine call's switch snapshot)
+    p.off32 = epilogue_off32(p);  // before the kernel choice: the 256 x 256 kernels' rules ask it
+    p.fgelu = sw.fast_gelu;       // (the engine call's switch snapshot)
     if (p.preb && (!hb || !p.Cb || (p.ldc2 & 1)))
         throw std::invalid_argument("gemm: bf16 pre-activation operands need the bf16-plane kernel with a Cb plane, ldc2 even");
     if (hb && p.segK > 0 && (p.segK % 8 || p.pad < 0 || (p.segB && (p.sBseg % 8))))
         throw std::invalid_argument("gemm: conv-A bf16 planes need segK and the tap stride % 8 == 0");
-    // conv weight gradients: the four-phase 256 x 256 TN form on grids that fill the chip (>= 256 tiles of 256^2; a
-    // smaller grid keeps the 128 x 128 kernel with its split-K)
-    const bool hbt4 = hbt && g_force_tile < 0 && hbt4_ok(p) &&
-                      (suta_switches().hbt4 == 2 || (long)((p.M + 255) / 256) * ((p.N + 255) / 256) * p.Z >= 256);
-    const int f32p = use_f32p(p);  // the fp32 four-phase 256 x 256 form (0: none)
-    int tile = f32p ? 8
-               : hbt ? (hbt4 ? 8 : 0)
-               : (hb && p.segK > 0) ? (g_force_tile < 0 && use_hbp_conv(p) ? 8 : 0)
-               : g_force_tile >= 0 ? g_force_tile
-               : hb            ? (use_hbx(p) ? 8 : choose_tile_hb(p.M, p.N, p.Z))
-               : p.mode == 2   ? choose_tile_bf16(p.M, p.N, p.Z, !bf16_gbf)
-                               : choose_tile(p.M, p.N, p.Z, p.K, p.mode);
-    if ((tile == 8 || tile == 9) && !(hb && p.K % 32 == 0 && p.K >= 128 && p.segK == 0 && (p.Z == 1 || (tile == 8 && hbx_batch_ok(p)))) &&
-        !(tile == 8 && hb && p.segK > 0 && hbp_conv_ok(p)) && !(tile == 8 && hbt) && !f32p)
-        tile = 0;
-    if (tile == 6 || tile == 7) tile = 0;  // (the removed 256 x 256 ping-pong and 160 x 128 tiles: DESIGN.md 8)
-    // tiles 0 = 128x128, 1 = 128x64, 2 = 64x128, 3 = 64x64; bf16 mode also 4 = 256x128, 5 = 128x256
-    // 8 / 9: the 256 x 256 slice-ring bf16-plane kernel (gemm_hbx.hip) on v_mfma_f32_32x32x16_bf16 / 16x16x32
-    const bool big = tile == 4 || tile == 8 || tile == 9;
-    const int BM = big ? 256 : (tile == 0 || tile == 1 || tile == 5) ? 128 : 64;
-    const int BN = (tile == 5 || tile == 8 || tile == 9) ? 256 : (tile == 0 || tile == 2 || tile == 4) ? 128 : 64;
-    const int gx = (p.N + BN - 1) / BN, gy = (p.M + BM - 1) / BM;
-    const long blocks = (long)gx * gy * p.Z;
 
+    // the family and its tile.  The first three rows never take a forced tile; the others take forced_tile where one
+    // is set, except that a forced 256 x 256 request the kernels cannot run falls back to 128 x 128 (g_tile) -- the
+    // unforced choices ask the same hbx_can_run.
+    GemmRoute r{};
+    TileCand t = {128, 128, 1.0};
+    const bool x256 = g_tile256 && hb && hbx_can_run(p, g_tile256);  // a forced 256 x 256 request that can run
+    if (f32p_wins(p)) {
+        r.family = GF_F32P;
+    } else if (hbt) {
+        // conv weight gradients: the four-phase 256 x 256 TN form on grids that fill the chip (a smaller grid keeps
+        // the 128 x 128 kernel with its split-K); SUTA_HBT4=2: on every grid (tests)
+        r.family = (!g_forced && hbt4_ok(p) && (sw.hbt4 == 2 || fills_256_round(p))) ? GF_HBT4 : GF_HBT;
+    } else if (hb && p.segK > 0) {
+        r.family = (!g_forced && hbx_conv_wins(p)) ? GF_HBX : GF_HB;
+    } else if (hb) {
+        r.family = x256 ? (g_tile256 == 16 ? GF_HBX16 : GF_HBX) : (!g_forced && hbx_wins(p)) ? GF_HBX : GF_HB;
+        t = g_forced ? g_tile : best_tile(HB_TILES, p, 512, true);
+    } else if (p.mode == 2) {
+        // bf16 products from fp32 operands: the register-staged one-plane kernel; weight gradients (transposed A)
+        // on register-converted LDS-DMA stages, which have no 256 x 128 tile (benchmark variants 3 / 8 force them)
+        const bool bf16_gbf = glds_ok && p.ta;
+        t = g_forced ? g_tile : best_tile(BF16_TILES, p, 512, true, bf16_gbf ? 128 : 256);
+        const bool gbf = glds_ok && t.bm + t.bn <= 256 && (g_forced ? (g_nbuf == 3 || g_nbuf == 8) : bf16_gbf);
+        r.family = gbf ? GF_GBF : GF_X6_1PLANE;
+    } else {
+        // fp32-accurate: x6 (register splits on LDS-DMA stages: benchmark variants 9 / 10) or exact fp32 on the
+        // LDS-DMA kernel where its loader's alignment holds
+        r.family = p.mode == 1 ? ((glds_ok && g_nbuf >= 9) ? GF_GBF_X6 : GF_X6)
+                               : ((glds_ok && g_nbuf >= 3) ? GF_GLDS : GF_F32);
+        t = g_forced ? g_tile : best_tile(p.mode == 1 ? X6_TILES : GLDS_TILES, p, 256, false);
+    }
+    const bool is256 = r.family == GF_F32P || r.family == GF_HBT4 || r.family == GF_HBX || r.family == GF_HBX16;
+    // (256 x 128 and 128 x 256 exist in the hb and x6_1plane families only; forced elsewhere: 128 x 128)
+    if (t.bm + t.bn > 256 && r.family != GF_HB && r.family != GF_X6_1PLANE) t = {128, 128, 1.0};
+    r.BM = is256 ? 256 : t.bm;
+    r.BN = is256 ? 256 : t.bn;
+    if (is256) hbx_resolve(r, p);
+    else stage_override(r);
+    if (r.family == GF_HB && p.segK > 0) r.stages = 2, r.bk = 32;  // (conv-A rows: the one instantiation)
+
+    r.gx = (p.N + r.BN - 1) / r.BN;
+    r.gy = (p.M + r.BM - 1) / r.BM;
+    const long blocks = (long)r.gx * r.gy * p.Z;
     // split-K when the grid cannot fill 256 CUs and K is long
+    // (the 256 x 256 kernels do not split; the split-K reduce has no bf16 pre store and no batched bf16 C plane)
     int splits = 1;
-    // (the split-K reduce has no bf16 pre store and no batched bf16 C plane)
-    if (ws && suta_switches().splitk && p.K >= 1024 && blocks < 256 && tile != 8 && tile != 9 && !p.preb &&
-        !(p.Cb && p.Z > 1)) {
+    if (have_ws && sw.splitk && p.K >= 1024 && blocks < 256 && !is256 && !p.preb && !(p.Cb && p.Z > 1)) {
         splits = (int)std::min<long>(16, (512 + blocks - 1) / blocks);
         while (splits > 1 && (long)splits * p.Z * p.M * (long)p.N > ws_floats) --splits;
         splits = std::min(splits, std::max(1, (p.K + 255) / 256));  // >= 256 K per split
     }
-    p.kchunk = splits > 1 ? (((p.K + splits - 1) / splits + BK - 1) / BK) * BK : p.K;
-    if (splits > 1) splits = (p.K + p.kchunk - 1) / p.kchunk;
-    p.splits = splits;
-    p.ws = ws;
-    if ((p.epi & EPI_DELTA) && !(tile == 8 && suta_switches().hbx_t && hbx_t_ok(p, true)))
+    r.kchunk = splits > 1 ? (((p.K + splits - 1) / splits + BK - 1) / BK) * BK : p.K;
+    if (splits > 1) splits = (p.K + r.kchunk - 1) / r.kchunk;
+    r.splits = splits;
+    // tile order (xcd_tile): n-fastest by default (m-fastest and other band widths measured 1-4 % slower on the
+    // fp32 linears).  bf16-plane GEMMs: bands of 8 tile rows (N >= 2048) or 4 walked column by column keep both operand
+    // panels L2-resident (tools/hb_bench, M = 25 536: qkv 543 -> 598 TF, ffn1 525 -> 590, the N = 1024
+    // shapes within +-2 %); the fp32 kernels measured neutral and keep the n-fastest order
+    r.order = 0;
+    if (hb && splits == 1) r.order = r.gx >= 16 ? 8 : 4;
+    // fp32 linears with >= 16 column tiles (QKV, FFN1 and their input-gradient GEMMs): their weight panels do
+    // not stay in an XCD's 4 MB L2 across a band of rows in n-fastest order; bands of 8 tile rows walked
+    // column by column halve their HBM reads (FFN1 forward 1.43 -> 0.72 GB per launch, PMC) at equal time
+    // (37.05 vs 37.13 utt/s, within noise); narrow GEMMs (6 column tiles) keep the n-fastest order, which
+    // reads less for them
+    if (!hb && p.mode == 0 && splits == 1 && p.Z == 1 && r.gx >= 16) r.order = 8;
+    r.gz = p.Z * splits;
+    r.off32 = p.off32;
+    r.fgelu = p.fgelu;
+    r.va = p.va;
+    r.vb = p.vb;
+    return r;
+}
+
+bool gemm_hbx_t_selected(const GemmParams& p) { return gemm_route_hbx_t(gemm_route(p, false, 0)); }
+
+void gemm_launch(GemmParams p, hipStream_t st, float* ws, long ws_floats) {
+    if (p.M <= 0 || p.N <= 0 || p.Z <= 0) return;
+    const GemmRoute r = gemm_route(p, ws != nullptr, ws_floats);
+    if ((p.epi & EPI_DELTA) && !gemm_route_hbx_t(r))
         throw std::invalid_argument("gemm: EPI_DELTA needs the 256 x 256 bf16-plane kernel's C^T epilogue (gemm_hbx_t_selected)");
-    {
-        // tile order (xcd_tile): n-fastest by default (m-fastest and other band widths measured 1-4 % slower on the
-        // fp32 linears).  bf16-plane GEMMs: bands of 8 tile rows (N >= 2048) or 4 walked column by column keep both operand
-        // panels L2-resident (tools/hb_bench, M = 25 536: qkv 543 -> 598 TF, ffn1 525 -> 590, the N = 1024
-        // shapes within +-2 %); the fp32 kernels measured neutral and keep the n-fastest order
-        p.order = 0;
-        if (hb && splits == 1) p.order = gx >= 16 ? 8 : 4;
-        // fp32 linears with >= 16 column tiles (QKV, FFN1 and their input-gradient GEMMs): their weight panels do
-        // not stay in an XCD's 4 MB L2 across a band of rows in n-fastest order; bands of 8 tile rows walked
-        // column by column halve their HBM reads (FFN1 forward 1.43 -> 0.72 GB per launch, PMC) at equal time
-        // (37.05 vs 37.13 utt/s, within noise); narrow GEMMs (6 column tiles) keep the n-fastest order, which
-        // reads less for them
-        if (!hb && p.mode == 0 && splits == 1 && p.Z == 1 && gx >= 16) p.order = 8;
+    p.va = r.va, p.vb = r.vb, p.off32 = r.off32, p.fgelu = r.fgelu;
+    p.splits = r.splits, p.kchunk = r.kchunk, p.order = r.order, p.ws = ws;
+    census(r, p);
+    const dim3 grid(r.gx, r.gy, r.gz);
+    switch (r.family) {
+    case GF_F32: gemm_run_f32(r.BM, r.BN, r.stages, p, grid, st); break;
+    case GF_GLDS: gemm_run_glds(r.BM, r.BN, r.bk, r.stages, p, grid, st); break;
+    case GF_X6: gemm_run_x6(r.BM, r.BN, r.bk, 3, p, grid, st); break;
+    case GF_X6_1PLANE: gemm_run_x6(r.BM, r.BN, r.bk, 1, p, grid, st); break;
+    case GF_GBF: gemm_run_gbf(r.BM, r.BN, r.bk, 1, p, grid, st); break;
+    case GF_GBF_X6: gemm_run_gbf(r.BM, r.BN, r.bk, 6, p, grid, st); break;
+    case GF_HB: gemm_run_hb(r.BM, r.BN, r.stages, r.bk, p, grid, st); break;
+    case GF_HBT: gemm_run_hbt(p, grid, st); break;
+    case GF_HBT4: case GF_HBX: case GF_HBX16: case GF_F32P: gemm_run_256(r, p, grid, st); break;
     }
-    dim3 grid(gx, gy, p.Z * splits);
-    if (f32p) {
-        census("f32p", BM, BN, p, splits);
-        gemm_run_f32p(p, grid, st);
-    } else if (hbt && tile == 8) {
-        census("hbt4", BM, BN, p, splits);
-        gemm_run_hbt4(p, grid, st);
-    } else if (hbt) {
-        census("hbt", BM, BN, p, splits);
-        gemm_run_hbt(p, grid, st);
-    } else if (hb) {
-        // SUTA_HB_NS: stage variant of the 128 x 128 bf16-plane kernel (A/B runs; 2 default), read once (thread-safe)
-        static const int hbns = [] {
-            const char* ev = std::getenv("SUTA_HB_NS");
-            return ev ? std::max(2, atoi(ev)) : 2;
-        }();
-        const int ns = g_force_tile >= 0 ? g_nbuf : (tile == 0 ? hbns : 2);
-        if (tile == 8 || tile == 9) {
-            census(tile == 8 ? "hbx" : "hbx16", BM, BN, p, splits);
-            gemm_run_hbx(tile == 8 ? 1 : 2, p, grid, st);
-        } else {
-            census("hb", BM, BN, p, splits);
-            gemm_run_hb(tile, ns, p, grid, st);
-        }
-    } else if (p.mode == 2) {
-        // bf16: register-staged one-plane kernel; weight gradients (and benchmark variants 3 / 8) on
-        // register-converted LDS-DMA stages (8 = BK64 x 2)
-        const bool gbf = glds_ok && tile < 4 && (g_force_tile >= 0 ? (g_nbuf == 3 || g_nbuf == 8) : bf16_gbf);
-        census(gbf ? "gbf" : "x6_1plane", BM, BN, p, splits);
-        if (gbf) gemm_run_gbf(g_nbuf == 8, 1, tile, p, grid, st);
-        else gemm_run_x6(tile, 0, 1, p, grid, st);
-    } else if (p.mode == 1 && glds_ok && g_nbuf >= 9) {
-        // x6 with register splits on LDS-DMA stages (benchmark variants 9 = BK32 x 2, 10 = BK64 x 2)
-        census("gbf_x6", BM, BN, p, splits);
-        gemm_run_gbf(g_nbuf == 10, 6, tile, p, grid, st);
-    } else if (p.mode == 1) {
-        // x6 planes: g_nbuf 2 -> BK 16 double-buffered; else BK 32 single LDS stage
-        census("x6", BM, BN, p, splits);
-        gemm_run_x6(tile, g_nbuf == 2, 3, p, grid, st);
-    } else if (g_nbuf >= 3 && glds_ok) {
-        // LDS-DMA variants: 3 = BK32 x 2 stages, 4 = BK16 x 4, 5 = BK16 x 3, 6 = BK32 x 3, 7 = BK64 x 2
-        census("glds", BM, BN, p, splits);
-        gemm_run_glds(g_nbuf, tile, p, grid, st);
-    } else {
-        census("f32", BM, BN, p, splits);
-        gemm_run_f32(tile, g_nbuf == 2 ? 2 : 1, p, grid, st);
-    }
-    if (splits > 1) {
+    if (r.splits > 1) {
         const long MN = (long)p.M * p.N;
         const int gxr = (int)std::min<long>(1024, (MN + 255) / 256);
         hipLaunchKernelGGL(gemm_splitk_reduce, dim3(gxr, p.Z), dim3(256), 0, st, p);

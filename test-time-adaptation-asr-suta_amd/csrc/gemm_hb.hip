@@ -2,47 +2,34 @@
 #include "gemm_kernels.h"
 #include <cstdlib>
 
-// ns: 2 (default) | 3 = three LDS stages | 4 = 128-deep bf16 K-steps, two stages (benchmark variants,
-// tools/hb_bench); tile 4 = 256x128, 5 = 128x256 (benchmark only)
-void gemm_run_hb(int tile, int ns, const GemmParams& p, dim3 grid, hipStream_t st) {
-    if (p.segK > 0) {  // conv input gradient on bf16 planes (128 x 128, conv-A rows, per-tap B segments)
+// stages x K-step (4-byte units, two bf16 each): 2 x 32 (default; at 128 x 128 the epilogue-class kernels of
+// gemm_hb_ep.hip) | 3 x 32 | 2 x 64 | 4 x 16 and 3 x 16 (128 x 128 only; 16-KB stages) -- the benchmark variants of
+// tools/hb_bench, as the 256 x 128 and 128 x 256 tiles (2 x 32 only)
+void gemm_run_hb(int BM, int BN, int stages, int bk, const GemmParams& p, dim3 grid, hipStream_t st) {
+    const bool t128 = BM == 128 && BN == 128;
+    if (p.segK > 0) {  // conv input gradient on bf16 planes (conv-A rows, per-tap B segments)
+        if (!t128 || stages != 2 || bk != 32) throw std::invalid_argument("hb: conv-A rows only at 128 x 128, 2 x 32");
         if (p.segB) launch_hb<128, 128, 2, 32, 4, true, true>(p, grid, st);
         else launch_hb<128, 128, 2, 32, 4, true, false>(p, grid, st);
-        return;
-    }
-    if (tile == 4) {
+    } else if (BM == 256 && BN == 128) {
         launch_hb<256, 128, 2>(p, grid, st);
-        return;
-    }
-    if (tile == 5) {
+    } else if (BM == 128 && BN == 256) {
         launch_hb<128, 256, 2>(p, grid, st);
-        return;
+    } else if (bk == 16 && t128 && stages == 4) {
+        launch_hb<128, 128, 4, 16>(p, grid, st);
+    } else if (bk == 16 && t128 && stages == 3) {
+        launch_hb<128, 128, 3, 16>(p, grid, st);
+    } else if (stages == 2 && bk == 32 && t128 && gemm_run_hb_class(p, grid, st)) {
+        // (launched on its epilogue class's kernel)
+    } else {
+        with_tile128(BM, BN, [&](auto bm, auto bn) {
+            constexpr int M = decltype(bm)::value, N = decltype(bn)::value;
+            if (stages == 2 && bk == 64) launch_hb<M, N, 2, 64>(p, grid, st);
+            else if (stages == 3 && bk == 32) launch_hb<M, N, 3>(p, grid, st);
+            else if (stages == 2 && bk == 32) launch_hb<M, N, 2>(p, grid, st);
+            else throw std::invalid_argument("hb: no such stage variant");
+        });
     }
-
-    if (ns == 5 || ns == 6) {  // 32-deep bf16 K-steps: 4 (ns 5) or 3 (ns 6) LDS stages of 16 KB at 128 x 128
-        if (ns == 5) launch_hb<128, 128, 4, 16>(p, grid, st);
-        else launch_hb<128, 128, 3, 16>(p, grid, st);
-        return;
-    }
-    if (ns == 4) {
-        if (tile == 0) launch_hb<128, 128, 2, 64>(p, grid, st);
-        else if (tile == 1) launch_hb<128, 64, 2, 64>(p, grid, st);
-        else if (tile == 2) launch_hb<64, 128, 2, 64>(p, grid, st);
-        else launch_hb<64, 64, 2, 64>(p, grid, st);
-        return;
-    }
-    if (ns == 3) {
-        if (tile == 0) launch_hb<128, 128, 3>(p, grid, st);
-        else if (tile == 1) launch_hb<128, 64, 3>(p, grid, st);
-        else if (tile == 2) launch_hb<64, 128, 3>(p, grid, st);
-        else launch_hb<64, 64, 3>(p, grid, st);
-        return;
-    }
-    if (tile == 0 && gemm_run_hb_class(p, grid, st)) return;
-    if (tile == 0) launch_hb<128, 128, 2>(p, grid, st);
-    else if (tile == 1) launch_hb<128, 64, 2>(p, grid, st);
-    else if (tile == 2) launch_hb<64, 128, 2>(p, grid, st);
-    else launch_hb<64, 64, 2>(p, grid, st);
 }
 
 namespace {

@@ -94,7 +94,7 @@ struct XFr<16> {
 // pre-activation store, GELU', ragged row mask; fp32 C and / or the bf16 C plane; bf16 pre-activation operands) with
 // the same operations in the same order as gemm_epilogue; interior tiles with 32-bit offsets (scalar row bases +
 // one lane offset per fragment), edge tiles element by element with bounds checks.  No split-K, ACCUM or SMBWD
-// (gemm_run_hbx checks).
+// (hbx_resolve checks).
 template <int FM, int FN, bool CB, int EM>
 __device__ __forceinline__ void epilogue16(const GemmParams& p, const f32x4 (&acc)[FM][FN], int rbase, int cbase,
                                            int lane, bool interior) {
@@ -231,7 +231,7 @@ __device__ __forceinline__ void epilogue16(const GemmParams& p, const f32x4 (&ac
 // (C plane, pre-activation store, GELU' operand) moves in 16-B accesses and fp32 operands in float4s: 16 store
 // instructions per bf16 plane per wave instead of 128 two-lane-pair dword stores.  Same operations in the same order
 // as gemm_epilogue (elementwise; packed GELU pairs are lane-independent).  Rows past M are predicated per lane;
-// column tiles past N take the element-wise path.  gemm_run_hbx checks alignment (16-B bases, ld % 8 for the bf16
+// column tiles past N take the element-wise path.  hbx_resolve checks alignment (16-B bases, ld % 8 for the bf16
 // planes, % 4 for the fp32 ones) and off32 before choosing this form.
 typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
@@ -901,7 +901,7 @@ __device__ __forceinline__ int hbp_swz(int r) { return (r >> 1) & 7; }
 // counted wait per K-tile (below); 4: form 3's schedule on v_mfma_f32_16x16x32_bf16 (16 MFMAs per phase instead of 8
 // of 32x32x16, the guide's 256^2 template shape), accumulators remapped through LDS to the 32x32 C^T layout of
 // epilogue_t after the main loop (round 6).
-// CONV: conv-A rows with per-tap weight segments (the conv stack's input gradients, gemm.hip use_hbp_conv): A(m, k) =
+// CONV: conv-A rows with per-tap weight segments (the conv stack's input gradients, gemm.hip hbx_conv_wins): A(m, k) =
 // Ab[(m + seg - pad) ldab + k - seg segK], zero unless 0 <= m + seg - pad < Mvalid (per utterance: zmvalid), B(k, n) =
 // Bb[n ldbb + k - seg segK + seg sBseg], seg = k / segK.  With ldab == segK the A address is linear in k (a segment
 // step is one row down and back to column 0), so only the row's validity changes per segment; the B address jumps by
@@ -923,7 +923,7 @@ __device__ __forceinline__ int hbp_swz(int r) { return (r >> 1) & 7; }
 // past K read the zero page.  The quadrants, phases, waits and epilogue are form 4's.
 __device__ __forceinline__ int tn_swz(int r) { return 2 * ((r & 3) | (((r >> 3) & 1) << 2)); }
 
-// F32 (form 3 only; gemm_run_f32p): exact-fp32 operands p.A / p.B on v_mfma_f32_32x32x2_f32, bitwise gemm_glds_kernel<..., 32,
+// F32 (form 3 only; f32p_form): exact-fp32 operands p.A / p.B on v_mfma_f32_32x32x2_f32, bitwise gemm_glds_kernel<..., 32,
 // 2>'s results.  A K-tile is 32 floats, so a half-tile image is the same 128 rows x 128 B and the DMA pieces, swizzle,
 // phases, waits and barriers are the bf16 form's; addresses below are kept in 2-byte units (an fp32 leading dimension
 // counts twice).  A 16-B fragment read holds the 4 consecutive k of four MFMAs: lane half h reads chunk 4 h + kk, i.e.
@@ -1366,19 +1366,49 @@ __global__ __launch_bounds__(512, 1) void gemm_hbp_kernel(GemmParams p) {
     hbp_tile<CB, EM, FORM, CONV, DBG, TN, F32>(p, xcd_tile(p.order), reinterpret_cast<char*>(smem));
 }
 
-template <int MS, int EM, int TR = 0>
-void launch_hbx_em(const GemmParams& p, dim3 grid, hipStream_t st) {
-    if (p.Cb) hipLaunchKernelGGL((gemm_hbx_kernel<MS, true, EM, TR>), grid, dim3(512), 0, st, p);
-    else hipLaunchKernelGGL((gemm_hbx_kernel<MS, false, EM, TR>), grid, dim3(512), 0, st, p);
+// ---- host side: the eligibility rules gemm_route asks, the variant of a route, its launch ----
+
+// epilogue classes of the bf16 linears (as gemm_hb_ep.hip): bias / residual, bias + GELU + pre-activation store,
+// GELU'; ragged row masks in each
+constexpr int XEM_A = EPI_BIAS | EPI_RESID | EPI_ROWMASK;
+constexpr int XEM_G = EPI_BIAS | EPI_GELU | EPI_STORE_PRE | EPI_ROWMASK;
+constexpr int XEM_D = EPI_DGELU | EPI_ROWMASK;
+constexpr int XEM_L = EPI_DELTA;  // the attention out-projection's input gradient with the flash backward's delta
+// the class whose kernels carry the flags e (-1: none does)
+int epi_class(int e) {
+    return e == XEM_L ? XEM_L : !(e & ~XEM_A) ? XEM_A : !(e & ~XEM_G) ? XEM_G : !(e & ~XEM_D) ? XEM_D : -1;
 }
 
-// operands of the row-per-lane epilogue: 16-B bases, leading dimensions in whole 16-B chunks
+// SUTA_HBX_DBG: the kernels with parts of their main loop or epilogue removed (wrong results; tools/hb_bench
+// diagnostics of where the time goes).  Compiled only into the tools build (-DSUTA_HBX_DIAG), never into libsuta.so:
+// there the switch reads as 0, and every rule below that excludes the diagnostics is the same rule without them.
+int hbx_diag() {
+#ifdef SUTA_HBX_DIAG
+    return suta_switches().hbx_dbg;
+#else
+    return 0;
+#endif
+}
+
+template <class CB, class EM, class FORM, class CONV = std::false_type, class DBG = IntC<0>, class TN = std::false_type,
+          class F32 = IntC<0>>
+bool launch_hbp(const GemmParams& p, dim3 grid, hipStream_t st) {
+    hipLaunchKernelGGL((gemm_hbp_kernel<CB::value, EM::value, FORM::value, CONV::value, DBG::value, TN::value, F32::value>),
+                       grid, dim3(512), 0, st, p);
+    return true;
+}
+template <int MS, class CB, class EM, class TR, class DBG = IntC<0>>
+bool launch_hbx(const GemmParams& p, dim3 grid, hipStream_t st) {
+    hipLaunchKernelGGL((gemm_hbx_kernel<MS, CB::value, EM::value, TR::value, DBG::value>), grid, dim3(512), 0, st, p);
+    return true;
+}
+
 }  // namespace
 
-bool hbx_t_ok(const GemmParams& p, bool check_off32) {
+// operands of the row-per-lane epilogue: 16-B bases, leading dimensions in whole 16-B chunks
+bool hbx_t_ok(const GemmParams& p) {
     auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     const int e = p.epi;
-    if (check_off32 && !p.off32) return false;
     if ((!p.Cb || p.C) && !(a16(p.C) && p.ldc % 4 == 0)) return false;
     if (p.Cb && !(a16(p.Cb) && p.ldcb % 8 == 0)) return false;
     if ((e & EPI_BIAS) && !a16(p.bias)) return false;
@@ -1401,204 +1431,151 @@ bool hbx_t_ok(const GemmParams& p, bool check_off32) {
     return true;
 }
 
+// (a batched GEMM without the 32-bit-offset epilogue -- an operand over 4 GiB, or SUTA_EPI_FAST=0 -- fails this and
+// stays on the 128 x 128 kernel: gemm_hbp_kernel rebases its operands per batch, gemm_hbx_kernel has no batch)
+bool hbx_four_phase_ok(const GemmParams& p) {
+    const SutaSwitches& sw = suta_switches();
+    return sw.hbx_form && sw.hbx_t == 2 && p.K % 64 == 0 && p.off32 && hbx_t_ok(p) && !hbx_diag() &&
+           epi_class(p.epi) != -1;  // (its kernels are compiled per epilogue class only)
+}
+
 // the conv stack's input-gradient GEMMs (conv-A rows, per-tap bf16 weight segments) on the four-phase 256 x 256 kernel:
 // k-contiguous planes whose A rows are the segments (ldab == segK, segK % 64 == 0, segmented B, no batch split inside a
-// plane), the staggered main loop (SUTA_HBX_FORM 2 / 3) with the staged C^T epilogue, the plain epilogue class
-// SUTA_HBX_DBG: gemm_hbx_kernel with parts of its main loop removed (wrong results; tools/hb_bench diagnostics of
-// where the loop's time goes).  Compiled only into the tools build (-DSUTA_HBX_DIAG), never into libsuta.so.
-static int hbx_diag() {
-#ifdef SUTA_HBX_DIAG
-    return suta_switches().hbx_dbg;
-#else
-    return 0;
-#endif
-}
-
+// plane), the staggered main loop (SUTA_HBX_FORM 2 / 3 / 4) with the staged C^T epilogue, the plain epilogue class
 bool hbp_conv_ok(const GemmParams& p) {
-    const SutaSwitches& sw = suta_switches();
-    return p.segK > 0 && p.segB && p.segK % 64 == 0 && p.ldab == p.segK && p.pad >= 0 && p.K % 64 == 0 && p.K >= 128 &&
-           p.zdiv == 1 && !p.ta && p.Ab && p.Bb && sw.hbx_form >= 2 && sw.hbx_t == 2 && !hbx_diag() &&
-           (p.epi & ~(EPI_BIAS | EPI_RESID | EPI_ROWMASK)) == 0 && !p.preb && p.splits <= 1 && hbx_t_ok(p, true);
+    return p.segK > 0 && p.segB && p.segK % 64 == 0 && p.ldab == p.segK && p.pad >= 0 && p.K >= 128 && p.zdiv == 1 &&
+           !p.ta && p.Ab && p.Bb && suta_switches().hbx_form >= 2 && epi_class(p.epi) == XEM_A && !p.preb &&
+           hbx_four_phase_ok(p);
 }
 
-namespace {
-
-// epilogue classes of the bf16 linears (as gemm_hb_ep.hip): bias / residual, bias + GELU + pre-activation store,
-// GELU'; ragged row masks in each
-constexpr int XEM_A = EPI_BIAS | EPI_RESID | EPI_ROWMASK;
-constexpr int XEM_G = EPI_BIAS | EPI_GELU | EPI_STORE_PRE | EPI_ROWMASK;
-constexpr int XEM_D = EPI_DGELU | EPI_ROWMASK;
-constexpr int XEM_L = EPI_DELTA;  // the attention out-projection's input gradient with the flash backward's delta
-
-}  // namespace
-
-// the conv stack's weight gradients (MN-contiguous bf16 planes, gemm.hip use_hbt4) on the four-phase 256 x 256 kernel's
-// TN form: fp32 C only, the plain / bias / residual class, no split-K, the staged C^T epilogue's operand conditions
+// the conv stack's weight gradients (MN-contiguous bf16 planes) on the four-phase 256 x 256 kernel's TN form: fp32 C
+// only, the plain / bias / residual class, the staged C^T epilogue's operand conditions (SUTA_HBT4=0: off)
 bool hbt4_ok(const GemmParams& p) {
     return suta_switches().hbt4 && p.ta && !p.tb && p.Ab && p.Bb && !p.Cb && p.segK == 0 && p.zdiv == 1 &&
-           p.splits <= 1 && (p.epi & ~(EPI_BIAS | EPI_RESID | EPI_ROWMASK)) == 0 && hbx_t_ok(p, true);
-}
-void gemm_run_hbt4(const GemmParams& p, dim3 grid, hipStream_t st) {
-    if (!hbt4_ok(p)) throw std::invalid_argument("hbt4: outside the TN form's conditions");
-    hipLaunchKernelGGL((gemm_hbp_kernel<false, EPI_BIAS | EPI_RESID | EPI_ROWMASK, 4, false, 0, true>), grid, dim3(512),
-                       0, st, p);
+           epi_class(p.epi) == XEM_A && p.off32 && hbx_t_ok(p);
 }
 
-// The exact-fp32 GEMMs on the four-phase 256 x 256 kernel (gemm_hbp_kernel's F32 forms, form-3 schedule; gemm.hip
-// use_f32p): 0 = not eligible, 1 = A and B k-contiguous (NT; with conv-A rows and per-tap weight segments: CONV),
+// The exact-fp32 GEMMs on the four-phase 256 x 256 kernel (gemm_hbp_kernel's F32 forms, form-3 schedule):
+// 0 = not eligible, 1 = A and B k-contiguous (NT; with conv-A rows and per-tap weight segments: CONV),
 // 2 = B row-contiguous (NN).  fp32 operands and outputs, 16-B aligned with leading dimensions and batch strides in
-// whole 16-B chunks, K a multiple of the 32-float K-tile with at least four of them, no split-K, one of the three
-// epilogue classes, 32-bit epilogue offsets (p.off32 set by the caller), the staged C^T epilogue's operand conditions.
+// whole 16-B chunks, K a multiple of the 32-float K-tile with at least four of them, one of the three epilogue classes
+// (CONV: not the GELU one), 32-bit epilogue offsets, the staged C^T epilogue's operand conditions.
 int f32p_form(const GemmParams& p) {
     auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const int e = p.epi;
+    const int em = epi_class(p.epi);
     if (p.mode != 0 || p.Ab || p.Bb || p.Cb || p.preb || p.ta || !p.A || !p.B || !p.C) return 0;
-    if (p.K % 32 || p.K < 128 || p.splits > 1 || !p.off32 || (e & (EPI_ACCUM | EPI_SMBWD | EPI_DELTA))) return 0;
-    if ((e & ~XEM_A) && (e & ~XEM_G) && (e & ~XEM_D)) return 0;
+    if (p.K % 32 || p.K < 128 || !p.off32 || em == -1 || em == XEM_L) return 0;
     if (!a16(p.A) || !a16(p.B) || p.lda % 4 || p.ldb % 4 || ((p.sA0 | p.sA1 | p.sB0 | p.sB1) % 4)) return 0;
     if (p.segK > 0) {  // conv-A rows are the segments; only with per-tap weight segments, k-contiguous
-        if (!p.segB || !p.tb || p.segK % 32 || p.lda != p.segK || p.pad < 0 || p.zdiv != 1 || p.sBseg % 4 || (e & ~XEM_A & ~XEM_D))
+        if (!p.segB || !p.tb || p.segK % 32 || p.lda != p.segK || p.pad < 0 || p.zdiv != 1 || p.sBseg % 4 || em == XEM_G)
             return 0;
     } else if (p.segB) {
         return 0;
     }
     GemmParams q = p;  // (hbx_t_ok asks the bf16 planes' 8-element batch strides of the operands: checked above)
     q.sA0 = q.sA1 = q.sB0 = q.sB1 = 0;
-    if (!hbx_t_ok(q, true)) return 0;
-    return p.tb ? 1 : 2;
+    return !hbx_t_ok(q) ? 0 : p.tb ? 1 : 2;
 }
 
-void gemm_run_f32p(const GemmParams& p, dim3 grid, hipStream_t st) {
-    const int form = f32p_form(p), e = p.epi;
-    if (!form) throw std::invalid_argument("f32p: outside the fp32 four-phase form's conditions");
-#define F32P(EM_, CONV_, F_) \
-    hipLaunchKernelGGL((gemm_hbp_kernel<false, EM_, 3, CONV_, 0, false, F_>), grid, dim3(512), 0, st, p)
-    if (p.segK > 0) {
-        if ((e & ~XEM_A) == 0) F32P(XEM_A, true, 1);
-        else F32P(XEM_D, true, 1);
-    } else if (form == 1) {
-        if ((e & ~XEM_A) == 0) F32P(XEM_A, false, 1);
-        else if ((e & ~XEM_G) == 0) F32P(XEM_G, false, 1);
-        else F32P(XEM_D, false, 1);
-    } else {
-        if ((e & ~XEM_A) == 0) F32P(XEM_A, false, 2);
-        else if ((e & ~XEM_G) == 0) F32P(XEM_G, false, 2);
-        else F32P(XEM_D, false, 2);
+// Which 256 x 256 kernel a route to r.family is: main loop, epilogue form, operand form, epilogue class.
+//   f32p, hbt4, and hbx on conv-A rows: gemm_hbp_kernel with the staged C^T epilogue (their *_ok rule holds).
+//   hbx16: gemm_hbx_kernel on v_mfma_f32_16x16x32_bf16 with epilogue16 (the linears' classes only).
+//   hbx: gemm_hbp_kernel where hbx_four_phase_ok and a class covers the epilogue; else gemm_hbx_kernel on
+//   v_mfma_f32_32x32x16_bf16 with C^T accumulators (SUTA_HBX_T 1: row-per-lane 16-B stores, 2: LDS-staged whole-line
+//   stores) where its operand conditions hold and a class covers the epilogue; else with the column-per-lane epilogue
+//   (class-specialised for the linears' classes, the generic one otherwise).
+// SUTA_HBX_FORM 4 (default): the 16x16x32 main loop on every shape (tools/hb_bench, profiles/r6/hb16.txt: +8-14 % on
+// the QKV, FFN1, FFN2 and dQKV shapes, the N = K = 1024 out-projection -4 % alone; in the C4 loop every shape on
+// form 4 measured +0.3 % over keeping form 3 for that one, profiles/r6/conv16)
+void hbx_resolve(GemmRoute& r, const GemmParams& p) {
+    const SutaSwitches& sw = suta_switches();
+    r.four_phase = true;
+    r.form = 3;
+    r.ct = 2;
+    r.conv = p.segK > 0;
+    r.tn = r.family == GF_HBT4;
+    r.f32 = r.family == GF_F32P ? (p.tb ? 1 : 2) : 0;
+    r.em = epi_class(p.epi);
+    r.dbg = 0;
+    if (r.family == GF_F32P) return;
+    if (r.tn || r.conv) {  // hbt4: form 4; conv-A rows: SUTA_HBX_FORM 2, 3 or 4 (hbp_conv_ok: at least 2)
+        r.form = r.tn ? 4 : std::min(sw.hbx_form, 4);
+        return;
     }
-#undef F32P
-}
-
-// variant 1: v_mfma_f32_32x32x16_bf16 with the shared epilogue (class-specialised kernels for the linears' epilogue
-// classes, the generic one otherwise); 2: v_mfma_f32_16x16x32_bf16 with epilogue16 (the linears' classes only)
-void gemm_run_hbx(int variant, const GemmParams& p, dim3 grid, hipStream_t st) {
-    const int e = p.epi;
-    if (p.splits > 1 || (e & (EPI_ACCUM | EPI_SMBWD)))
-        throw std::invalid_argument("hbx: no split-K, ACCUM or SMBWD");
-    if (p.Z != 1 && !(variant == 1 && suta_switches().hbx_form && suta_switches().hbx_t == 2 && p.K % 64 == 0 &&
-                      hbx_t_ok(p, true) && !hbx_diag()))
+    if (p.epi & (EPI_ACCUM | EPI_SMBWD)) throw std::invalid_argument("hbx: no split-K, ACCUM or SMBWD");
+    r.four_phase = r.family == GF_HBX && hbx_four_phase_ok(p);
+    if (p.Z != 1 && !r.four_phase)  // (gemm_hbx_kernel has no batch)
         throw std::invalid_argument("hbx: batched GEMMs only on the four-phase form with the staged C^T epilogue");
-    if (p.segK > 0) {  // conv-A rows: the four-phase form's CONV instantiation (gemm.hip hbp_conv_ok)
-        if (!hbp_conv_ok(p)) throw std::invalid_argument("hbx: conv-A GEMM outside the four-phase CONV form's conditions");
-        if (suta_switches().hbx_form >= 4) {
-            if (p.Cb) hipLaunchKernelGGL((gemm_hbp_kernel<true, XEM_A, 4, true>), grid, dim3(512), 0, st, p);
-            else hipLaunchKernelGGL((gemm_hbp_kernel<false, XEM_A, 4, true>), grid, dim3(512), 0, st, p);
-        } else if (suta_switches().hbx_form == 3) {
-            if (p.Cb) hipLaunchKernelGGL((gemm_hbp_kernel<true, XEM_A, 3, true>), grid, dim3(512), 0, st, p);
-            else hipLaunchKernelGGL((gemm_hbp_kernel<false, XEM_A, 3, true>), grid, dim3(512), 0, st, p);
-        } else {
-            if (p.Cb) hipLaunchKernelGGL((gemm_hbp_kernel<true, XEM_A, 2, true>), grid, dim3(512), 0, st, p);
-            else hipLaunchKernelGGL((gemm_hbp_kernel<false, XEM_A, 2, true>), grid, dim3(512), 0, st, p);
-        }
-        return;
-    }
-    if ((e & EPI_DELTA) && !(variant == 1 && suta_switches().hbx_t && hbx_t_ok(p, true)))
-        throw std::invalid_argument("hbx: EPI_DELTA needs the C^T epilogue and its operand conditions");
-    if (variant == 2) {
-        if ((e & ~XEM_A) == 0) launch_hbx_em<16, XEM_A>(p, grid, st);
-        else if ((e & ~XEM_G) == 0) launch_hbx_em<16, XEM_G>(p, grid, st);
-        else if ((e & ~XEM_D) == 0) launch_hbx_em<16, XEM_D>(p, grid, st);
-        else throw std::invalid_argument("hbx 16x16: epilogue flags outside the linears' classes");
-        return;
-    }
-    const int tr = suta_switches().hbx_t;
-    const int dbg = hbx_diag();
-    // SUTA_HBX_FORM 4 (default): the 16x16x32 form on every shape (tools/hb_bench, profiles/r6/hb16.txt: +8-14 % on
-    // the QKV, FFN1, FFN2 and dQKV shapes, the N = K = 1024 out-projection -4 % alone; in the C4 loop every shape on
-    // form 4 measured +0.3 % over keeping form 3 for that one, profiles/r6/conv16)
-    const int form = suta_switches().hbx_form;
-    if (form && tr == 2 && p.K % 64 == 0 && hbx_t_ok(p, true) && !dbg) {  // the four-phase K-tile schedule
-        const bool cb = p.Cb != nullptr;
-#define HBP(EM_)                                                                                                   \
-        do {                                                                                                       \
-            if (form == 4) {                                                                                       \
-                if (cb) hipLaunchKernelGGL((gemm_hbp_kernel<true, EM_, 4>), grid, dim3(512), 0, st, p);            \
-                else hipLaunchKernelGGL((gemm_hbp_kernel<false, EM_, 4>), grid, dim3(512), 0, st, p);              \
-            } else if (form == 3) {                                                                                \
-                if (cb) hipLaunchKernelGGL((gemm_hbp_kernel<true, EM_, 3>), grid, dim3(512), 0, st, p);            \
-                else hipLaunchKernelGGL((gemm_hbp_kernel<false, EM_, 3>), grid, dim3(512), 0, st, p);              \
-            } else if (form == 2) {                                                                                \
-                if (cb) hipLaunchKernelGGL((gemm_hbp_kernel<true, EM_, 2>), grid, dim3(512), 0, st, p);            \
-                else hipLaunchKernelGGL((gemm_hbp_kernel<false, EM_, 2>), grid, dim3(512), 0, st, p);              \
-            } else {                                                                                               \
-                if (cb) hipLaunchKernelGGL((gemm_hbp_kernel<true, EM_, 1>), grid, dim3(512), 0, st, p);            \
-                else hipLaunchKernelGGL((gemm_hbp_kernel<false, EM_, 1>), grid, dim3(512), 0, st, p);              \
-            }                                                                                                      \
-            return;                                                                                                \
-        } while (0)
-        if (e == XEM_L) HBP(XEM_L);
-        if ((e & ~XEM_A) == 0) HBP(XEM_A);
-        if ((e & ~XEM_G) == 0) HBP(XEM_G);
-        if ((e & ~XEM_D) == 0) HBP(XEM_D);
-#undef HBP
-    }
+    const bool ct = r.family == GF_HBX && sw.hbx_t && p.off32 && hbx_t_ok(p) && r.em != -1;
+    r.form = !r.four_phase ? 0 : (sw.hbx_form >= 2 && sw.hbx_form <= 4) ? sw.hbx_form : 1;
+    r.ct = r.four_phase ? 2 : ct ? sw.hbx_t : 0;
+    if (r.family == GF_HBX16 && (r.em == -1 || r.em == XEM_L))
+        throw std::invalid_argument("hbx 16x16: epilogue flags outside the linears' classes");
 #ifdef SUTA_HBX_DIAG
-    if (dbg >= 11 && dbg <= 17 && (e & ~XEM_A) == 0) {  // tools/hb_bench: gemm_hbp_kernel form 4 diagnostics
-        const bool cb = p.Cb != nullptr;
-#define HBP_DBG(D)                                                                                                 \
-        do {                                                                                                       \
-            if (cb) hipLaunchKernelGGL((gemm_hbp_kernel<true, XEM_A, 4, false, D>), grid, dim3(512), 0, st, p);    \
-            else hipLaunchKernelGGL((gemm_hbp_kernel<false, XEM_A, 4, false, D>), grid, dim3(512), 0, st, p);      \
-        } while (0)
-        if (dbg == 11) HBP_DBG(1);
-        else if (dbg == 12) HBP_DBG(2);
-        else if (dbg == 13) HBP_DBG(3);
-        else if (dbg == 14) HBP_DBG(20);
-        else if (dbg == 15) HBP_DBG(8);
-        else if (dbg == 16) HBP_DBG(16);
-        else HBP_DBG(32);
-#undef HBP_DBG
-        return;
-    }
-    if (dbg && tr == 2 && hbx_t_ok(p, true) && (e & ~XEM_A) == 0) {  // tools/hb_bench diagnostics
-        const bool cb = p.Cb != nullptr;
-#define HBX_DBG(D)                                                                                                 \
-        do {                                                                                                       \
-            if (cb) hipLaunchKernelGGL((gemm_hbx_kernel<32, true, XEM_A, 2, D>), grid, dim3(512), 0, st, p);       \
-            else hipLaunchKernelGGL((gemm_hbx_kernel<32, false, XEM_A, 2, D>), grid, dim3(512), 0, st, p);         \
-        } while (0)
-        if (dbg == 1) HBX_DBG(1);
-        else if (dbg == 2) HBX_DBG(2);
-        else if (dbg == 3) HBX_DBG(3);
-        else if (dbg == 4) HBX_DBG(4);
-        else HBX_DBG(5);
-#undef HBX_DBG
-        return;
+    const int dbg = hbx_diag();
+    if (r.family == GF_HBX && dbg >= 11 && dbg <= 17 && r.em == XEM_A) {  // gemm_hbp_kernel form 4 diagnostics
+        static const int d4[7] = {1, 2, 3, 20, 8, 16, 32};
+        r.four_phase = true, r.form = 4, r.ct = 2, r.dbg = d4[dbg - 11];
+    } else if (r.family == GF_HBX && dbg && r.ct == 2 && r.em == XEM_A) {  // gemm_hbx_kernel diagnostics
+        r.dbg = std::min(dbg, 5);
     }
 #endif
-    if (tr && hbx_t_ok(p, true)) {  // C^T accumulators, row-per-lane epilogue (2: LDS-staged whole-line stores)
-        if (tr == 2) {
-            if (e == XEM_L) return launch_hbx_em<32, XEM_L, 2>(p, grid, st);
-            if ((e & ~XEM_A) == 0) return launch_hbx_em<32, XEM_A, 2>(p, grid, st);
-            if ((e & ~XEM_G) == 0) return launch_hbx_em<32, XEM_G, 2>(p, grid, st);
-            if ((e & ~XEM_D) == 0) return launch_hbx_em<32, XEM_D, 2>(p, grid, st);
-        }
-        if (e == XEM_L) return launch_hbx_em<32, XEM_L, 1>(p, grid, st);
-        if ((e & ~XEM_A) == 0) return launch_hbx_em<32, XEM_A, 1>(p, grid, st);
-        if ((e & ~XEM_G) == 0) return launch_hbx_em<32, XEM_G, 1>(p, grid, st);
-        if ((e & ~XEM_D) == 0) return launch_hbx_em<32, XEM_D, 1>(p, grid, st);
-    }
-    if ((e & ~XEM_A) == 0) launch_hbx_em<32, XEM_A>(p, grid, st);
-    else if ((e & ~XEM_G) == 0) launch_hbx_em<32, XEM_G>(p, grid, st);
-    else if ((e & ~XEM_D) == 0) launch_hbx_em<32, XEM_D>(p, grid, st);
-    else launch_hbx_em<32, -1>(p, grid, st);
 }
+
+// Launches the instantiation the route names.  The lists below are the instantiations libsuta.so holds.
+void gemm_run_256(const GemmRoute& r, const GemmParams& p, dim3 grid, hipStream_t st) {
+    using T = std::true_type;
+    using F = std::false_type;
+    using A = IntC<XEM_A>;
+    bool ok = false;
+    auto cb_or_not = [&](auto&& f) { with_bool(p.Cb != nullptr, f); };
+    if (r.family == GF_HBT4) {
+        ok = launch_hbp<F, A, IntC<4>, F, IntC<0>, T>(p, grid, st);
+    } else if (r.family == GF_F32P && r.conv) {
+        with_int<XEM_A, XEM_D>(r.em, [&](auto em) {
+            ok = launch_hbp<F, decltype(em), IntC<3>, T, IntC<0>, F, IntC<1>>(p, grid, st);
+        });
+    } else if (r.family == GF_F32P) {
+        with_int<XEM_A, XEM_G, XEM_D>(r.em, [&](auto em) {
+            with_int<1, 2>(r.f32, [&](auto f32) {
+                ok = launch_hbp<F, decltype(em), IntC<3>, F, IntC<0>, F, decltype(f32)>(p, grid, st);
+            });
+        });
+    } else if (r.family == GF_HBX16) {
+        with_int<XEM_A, XEM_G, XEM_D>(r.em, [&](auto em) {
+            cb_or_not([&](auto cb) { ok = launch_hbx<16, decltype(cb), decltype(em), IntC<0>>(p, grid, st); });
+        });
+#ifdef SUTA_HBX_DIAG
+    } else if (r.dbg && r.four_phase) {
+        with_int<1, 2, 3, 20, 8, 16, 32>(r.dbg, [&](auto dbg) {
+            cb_or_not([&](auto cb) { ok = launch_hbp<decltype(cb), A, IntC<4>, F, decltype(dbg)>(p, grid, st); });
+        });
+    } else if (r.dbg) {
+        with_int<1, 2, 3, 4, 5>(r.dbg, [&](auto dbg) {
+            cb_or_not([&](auto cb) { ok = launch_hbx<32, decltype(cb), A, IntC<2>, decltype(dbg)>(p, grid, st); });
+        });
+#endif
+    } else if (r.four_phase && r.conv) {
+        with_int<2, 3, 4>(r.form, [&](auto form) {
+            cb_or_not([&](auto cb) { ok = launch_hbp<decltype(cb), A, decltype(form), T>(p, grid, st); });
+        });
+    } else if (r.four_phase) {
+        with_int<XEM_L, XEM_A, XEM_G, XEM_D>(r.em, [&](auto em) {
+            with_int<1, 2, 3, 4>(r.form, [&](auto form) {
+                cb_or_not([&](auto cb) { ok = launch_hbp<decltype(cb), decltype(em), decltype(form)>(p, grid, st); });
+            });
+        });
+    } else if (r.ct) {
+        with_int<XEM_L, XEM_A, XEM_G, XEM_D>(r.em, [&](auto em) {
+            with_int<1, 2>(r.ct, [&](auto tr) {
+                cb_or_not([&](auto cb) { ok = launch_hbx<32, decltype(cb), decltype(em), decltype(tr)>(p, grid, st); });
+            });
+        });
+    } else {
+        with_int<XEM_A, XEM_G, XEM_D, -1>(r.em == XEM_L ? -1 : r.em, [&](auto em) {
+            cb_or_not([&](auto cb) { ok = launch_hbx<32, decltype(cb), decltype(em), IntC<0>>(p, grid, st); });
+        });
+    }
+    if (!ok) throw std::invalid_argument("gemm: the route names no compiled 256 x 256 kernel");
+}
+

@@ -20,11 +20,35 @@
 #include "common.h"
 #include <algorithm>
 #include <stdexcept>
+#include <type_traits>
 
 #pragma once
 
 namespace {
 
+// Host dispatch from a run-time value of the route to a template argument: f receives a std::integral_constant,
+// so a launcher names its kernel once and only the listed values are instantiated.
+template <int V>
+using IntC = std::integral_constant<int, V>;
+// f(IntC<v>) when v is one of Vs (false: none is)
+template <int... Vs, class F>
+bool with_int(int v, F&& f) {
+    return ((v == Vs && (f(IntC<Vs>{}), true)) || ...);
+}
+template <class F>
+void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+// f(IntC<BM>, IntC<BN>) for the tiles of the 128 family: 128 x 128, 128 x 64, 64 x 128, 64 x 64
+template <class F>
+void with_tile128(int BM, int BN, F&& f) {
+    if (BM == 128 && BN == 128) f(IntC<128>{}, IntC<128>{});
+    else if (BM == 128 && BN == 64) f(IntC<128>{}, IntC<64>{});
+    else if (BM == 64 && BN == 128) f(IntC<64>{}, IntC<128>{});
+    else if (BM == 64 && BN == 64) f(IntC<64>{}, IntC<64>{});
+    else throw std::invalid_argument("gemm: no such tile in the 128 x 128 family");
+}
 
 constexpr int BK = 32;
 constexpr int LDK = BK + 4;
@@ -1488,11 +1512,10 @@ void launch_gbf(const GemmParams& p, dim3 grid, hipStream_t st) {
 }
 
 template <int BKS, int NS, int NPROD>
-void launch_gbf_tile(int tile, const GemmParams& p, dim3 grid, hipStream_t st) {
-    if (tile == 0) launch_gbf<128, 128, BKS, NS, NPROD>(p, grid, st);
-    else if (tile == 1) launch_gbf<128, 64, BKS, NS, NPROD>(p, grid, st);
-    else if (tile == 2) launch_gbf<64, 128, BKS, NS, NPROD>(p, grid, st);
-    else launch_gbf<64, 64, BKS, NS, NPROD>(p, grid, st);
+void launch_gbf_tile(int BM, int BN, const GemmParams& p, dim3 grid, hipStream_t st) {
+    with_tile128(BM, BN, [&](auto bm, auto bn) {
+        launch_gbf<decltype(bm)::value, decltype(bn)::value, BKS, NS, NPROD>(p, grid, st);
+    });
 }
 
 template <int BM, int BN, int BKS, int NS>
@@ -1511,11 +1534,10 @@ void launch_glds(const GemmParams& p, dim3 grid, hipStream_t st) {
 }
 
 template <int BKS, int NS>
-void launch_glds_tile(int tile, const GemmParams& p, dim3 grid, hipStream_t st) {
-    if (tile == 0) launch_glds<128, 128, BKS, NS>(p, grid, st);
-    else if (tile == 1) launch_glds<128, 64, BKS, NS>(p, grid, st);
-    else if (tile == 2) launch_glds<64, 128, BKS, NS>(p, grid, st);
-    else launch_glds<64, 64, BKS, NS>(p, grid, st);
+void launch_glds_tile(int BM, int BN, const GemmParams& p, dim3 grid, hipStream_t st) {
+    with_tile128(BM, BN, [&](auto bm, auto bn) {
+        launch_glds<decltype(bm)::value, decltype(bn)::value, BKS, NS>(p, grid, st);
+    });
 }
 
 template <int BM, int BN, int NBUF>
@@ -1665,10 +1687,11 @@ void launch_hb(const GemmParams& p, dim3 grid, hipStream_t st) {
 
 }  // namespace
 
-// Per-family launch wrappers (each defined in its own TU).
-void gemm_run_f32(int tile, int nbuf, const GemmParams& p, dim3 grid, hipStream_t st);      // gemm_f32.hip
-void gemm_run_x6(int tile, int bk16, int npl, const GemmParams& p, dim3 grid, hipStream_t st);  // gemm_x6.hip
-void gemm_run_glds(int variant, int tile, const GemmParams& p, dim3 grid, hipStream_t st);  // gemm_glds.hip
+// Per-family launch wrappers (each defined in its own TU): they launch the instantiation the route names (its tile,
+// LDS stages, K-step); a variant the family does not compile is a std::invalid_argument.
+void gemm_run_f32(int BM, int BN, int stages, const GemmParams& p, dim3 grid, hipStream_t st);         // gemm_f32.hip
+void gemm_run_x6(int BM, int BN, int bk, int npl, const GemmParams& p, dim3 grid, hipStream_t st);     // gemm_x6.hip
+void gemm_run_glds(int BM, int BN, int bk, int stages, const GemmParams& p, dim3 grid, hipStream_t st);  // gemm_glds.hip
 // ============================================================================================
 // bf16 GEMM on MN-contiguous bf16 planes ("hbt"; the conv weight gradients of config C4):
 //   A(m, k) = Ab[k * ldab + m], B(k, n) = Bb[k * ldbb + n]   (both row-major over k: im2col(a)^T and dz)
@@ -1795,17 +1818,25 @@ __global__ __launch_bounds__(256, 2) void gemm_hbt_kernel(GemmParams p) {
                                  m0 + BM <= p.M && n0 + BN <= p.N, tid.z);
 }
 
-void gemm_run_gbf(int bk64, int nprod, int tile, const GemmParams& p, dim3 grid, hipStream_t st);  // gemm_gbf.hip
-void gemm_run_hb(int tile, int ns, const GemmParams& p, dim3 grid, hipStream_t st);                         // gemm_hb.hip
-void gemm_run_hbt(const GemmParams& p, dim3 grid, hipStream_t st);                                          // gemm_hb.hip
-void gemm_run_hbx(int variant, const GemmParams& p, dim3 grid, hipStream_t st);                             // gemm_hbx.hip
-void gemm_run_hbt4(const GemmParams& p, dim3 grid, hipStream_t st);                                         // gemm_hbx.hip
-bool hbt4_ok(const GemmParams& p);  // the conv weight gradients on the four-phase kernel's TN form (gemm_hbx.hip)
-// the row-per-lane (C^T accumulator) epilogue's operand conditions (gemm_hbx.hip)
-bool hbx_t_ok(const GemmParams& p, bool check_off32);
-// conv-A GEMM (segK > 0) eligible for the four-phase 256 x 256 kernel's CONV form (gemm_hbx.hip; p.off32 set)
+void gemm_run_gbf(int BM, int BN, int bk, int nprod, const GemmParams& p, dim3 grid, hipStream_t st);  // gemm_gbf.hip
+void gemm_run_hb(int BM, int BN, int stages, int bk, const GemmParams& p, dim3 grid, hipStream_t st);  // gemm_hb.hip
+void gemm_run_hbt(const GemmParams& p, dim3 grid, hipStream_t st);                                     // gemm_hb.hip
+
+// The 256 x 256 families (gemm_hbx.hip): the eligibility rules gemm_route asks (p.off32 set), each stated once, ...
+// the C^T (row-per-lane) epilogue's operand conditions, apart from the 32-bit offsets (p.off32) its callers add
+bool hbx_t_ok(const GemmParams& p);
+// a bf16-plane linear may take gemm_hbp_kernel: SUTA_HBX_FORM on, the staged C^T epilogue and its conditions,
+// K in whole 64-deep tiles, an epilogue class.  The only form a batched (Z > 1) GEMM may take.
+bool hbx_four_phase_ok(const GemmParams& p);
+// conv-A GEMM (segK > 0) on bf16 planes eligible for gemm_hbp_kernel's CONV form
 bool hbp_conv_ok(const GemmParams& p);
-// exact-fp32 GEMM eligible for the four-phase 256 x 256 kernel's fp32 forms (gemm_hbx.hip; p.off32 set): 0 = no,
-// 1 = A and B k-contiguous (also conv-A rows with weight segments), 2 = B row-contiguous
+// MN-contiguous bf16 planes (the conv weight gradients) eligible for gemm_hbp_kernel's TN form
+bool hbt4_ok(const GemmParams& p);
+// exact-fp32 GEMM eligible for gemm_hbp_kernel's fp32 forms: 0 = no, 1 = A and B k-contiguous (also conv-A rows with
+// weight segments), 2 = B row-contiguous
 int f32p_form(const GemmParams& p);
-void gemm_run_f32p(const GemmParams& p, dim3 grid, hipStream_t st);
+// ... the kernel, main loop, epilogue form and class of a route to one of them (r.family set; the other fields of the
+// 256 x 256 families are filled in; std::invalid_argument where no instantiation serves p), ...
+void hbx_resolve(GemmRoute& r, const GemmParams& p);
+// ... and the launch of what the route says
+void gemm_run_256(const GemmRoute& r, const GemmParams& p, dim3 grid, hipStream_t st);
