@@ -160,6 +160,18 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+typedef __bf16 lnbf16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f32x4 load_bf16x4(const __bf16* src) {  // one 8-B load, exact widening
+    const lnbf16x4 b = *reinterpret_cast<const lnbf16x4*>(src);
+    return f32x4{(float)b[0], (float)b[1], (float)b[2], (float)b[3]};
+}
+__device__ __forceinline__ void store_bf16x4(__bf16* dst, f32x4 v) {  // RNE, one 8-B store
+    lnbf16x4 b;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) b[e] = (__bf16)v[e];
+    *reinterpret_cast<lnbf16x4*>(dst) = b;
+}
+
 // ------------------------------------------------------------------------------------------
 // GEMM:  C[z](m,n) = epi( sum_k A[z](m,k) * B[z](k,n) )         (fp32 in, fp32 MFMA accumulate)
 //   A(m,k) = A[m*lda + k]   (ta = 0)   or A[k*lda + m]   (ta = 1)

@@ -277,9 +277,9 @@ struct Plan {
     std::vector<int> h_n, h_T;
     // forward
     float *xraw, *x;
-    float *z[SUTA_MAX_CONV], *a[SUTA_MAX_CONV], *cxhat[SUTA_MAX_CONV], *crstd[SUTA_MAX_CONV], *cmean[SUTA_MAX_CONV];
+    float *z[SUTA_MAX_CONV], *a[SUTA_MAX_CONV], *crstd[SUTA_MAX_CONV], *cmean[SUTA_MAX_CONV];
     float *gn_mean, *gn_rstd;
-    float *fp_xhat, *fp_rstd, *fp_y, *h0, *pz, *e, *enc_xhat, *enc_rstd, *enc_y;
+    float *fp_rstd, *fp_y, *h0, *pz, *e, *enc_rstd, *enc_y;
     // data2vec-audio positional stack: per layer the conv output z_j (the LayerNorm's input) and its row mean / rstd,
     // kept for the backward; the layers' activations a_j ping-pong through two buffers (the last goes into e)
     float *stk_z[MAX_POS_STACK], *stk_mean[MAX_POS_STACK], *stk_rstd[MAX_POS_STACK], *stk_a[2];
@@ -541,8 +541,30 @@ struct suta_engine {
     // reads the plane; no weight gradient reads them): stable-LN outputs, gelu(FFN1), dU.  Only where every
     // producer and consumer takes its plane path (the vectorised LayerNorm widths, K % 8 == 0).  One predicate
     // for the forward and the backward.
-    bool fp32_acts_dead() const {
-        return use_planes() && (c.H == 512 || c.H == 768 || c.H == 1024) && c.F % 8 == 0;
+    bool fp32_acts_dead() const { return use_planes() && ln_vec_width(c.H) && c.F % 8 == 0; }
+    // ---- LayerNorm sites: each LayerNorm described once, for forward() and backward() alike (parameters and their
+    // gradients at the same offsets of P and G; which statistics a site keeps: see Plan) ----
+    LnSite ln_site(long og, long ob, int rows_per_utt, int D, float eps, bool gelu, float* xhat, float* mean,
+                   float* rstd) const {
+        return {P + og, P + ob, G + og, G + ob, Pn, Pn, rows_per_utt, plan.B, D, eps, gelu, xhat, mean, rstd};
+    }
+    LnSite conv_ln(int i) const {  // layer mode: GELU follows
+        return ln_site(o_cg[i], o_cbeta[i], plan.Lc[i], c.C[i], 1e-5f, true, nullptr, plan.cmean[i], plan.crstd[i]);
+    }
+    LnSite feat_proj_ln() const {
+        return ln_site(o_fpg, o_fpb, plan.T, c.C[c.nconv - 1], c.eps, false, nullptr, plan.fp_mean, plan.fp_rstd);
+    }
+    LnSite encoder_ln() const { return ln_site(o_eg, o_eb, plan.T, c.H, c.eps, false, nullptr, plan.enc_mean, plan.enc_rstd); }
+    LnSite layer_ln(int l, int which) const {
+        const LayerBufs& lb = plan.lay[l];
+        return which == 1 ? ln_site(o_l1g[l], o_l1b[l], plan.T, c.H, c.eps, false, lb.xhat1, lb.mean1, lb.rstd1)
+                          : ln_site(o_l2g[l], o_l2b[l], plan.T, c.H, c.eps, false, lb.xhat2, lb.mean2, lb.rstd2);
+    }
+    // conv i's output z_i, the conv LayerNorm's input: bf16 in place in its fp32 buffer with conv_z_bf16()
+    LnIn conv_z(int i) const { return conv_z_bf16() ? ln_bf16(plan.z[i]) : ln_f32(plan.z[i]); }
+    // a backward on the engine's partial-sum buffer; x: the LayerNorm's stored input (sites without x-hat)
+    LnBwd ln_bwd(LnIn dy, LnOut dx, LnIn x = {}, const float* resid = nullptr) const {
+        return {dy, x, /*post_aux*/ nullptr, resid, dx, plan.lnpart, plan.lnpart_floats, /*conv*/ nullptr};
     }
     // bf16 mode with planes: the FFN pre-activation u (stored by FFN1, read by the FFN2 input gradient's gelu')
     // kept in bf16 (SUTA_PRE_BF16=0: fp32, for A/B runs)
@@ -796,7 +818,6 @@ void suta_engine::build_plan(int B, long N) {
             const long n = (long)B * pl.Lc[i] * k.C[i];
             pl.z[i] = (i == 0 && !k.layer_mode) ? nullptr : ar.take<float>(n);  // group-mode conv0 is recomputed
             pl.a[i] = ar.take<float>(n);
-            pl.cxhat[i] = nullptr;
             if (k.layer_mode) {
                 pl.crstd[i] = ar.take<float>((size_t)B * pl.Lc[i]);
                 pl.cmean[i] = ar.take<float>((size_t)B * pl.Lc[i]);
@@ -807,7 +828,6 @@ void suta_engine::build_plan(int B, long N) {
         pl.gn_mean = ar.take<float>((size_t)B * k.C[0]);
         pl.gn_rstd = ar.take<float>((size_t)B * k.C[0]);
         const long C6 = k.C[k.nconv - 1];
-        pl.fp_xhat = nullptr;
         pl.fp_mean = ar.take<float>(BT);
         pl.fp_rstd = ar.take<float>(BT);
         pl.fp_y = ar.take<float>(BT * C6);
@@ -821,7 +841,6 @@ void suta_engine::build_plan(int B, long N) {
         }
         for (int j = 0; j < 2; ++j) pl.stk_a[j] = k.posD > 1 ? ar.take<float>(BT * H) : nullptr;
         pl.e = ar.take<float>(BT * H);
-        pl.enc_xhat = nullptr;
         pl.enc_mean = ar.take<float>(BT);
         pl.enc_rstd = ar.take<float>(BT);
         pl.enc_y = ar.take<float>(BT * H);
@@ -949,9 +968,7 @@ void suta_engine::forward(int B) {
     if (k.layer_mode) {
         timed(F_NORM, [&] {
             // with conv planes only the bf16 activation is read (the next conv GEMM and its weight gradient)
-            launch_layernorm_fwd(zbf ? nullptr : pl.z[0], P + o_cg[0], P + o_cbeta[0], Pn, pl.Lc[0],
-                                 cpl ? nullptr : pl.a[0], pl.cxhat[0], pl.crstd[0], B * pl.Lc[0], k.C[0], 1e-5f, 1, st,
-                                 cpl ? conv_act_plane(0) : nullptr, pl.cmean[0], zbf ? pl.z[0] : nullptr);
+            ln_forward(conv_ln(0), {conv_z(0), cpl ? ln_plane(conv_act_plane(0)) : ln_out(pl.a[0])}, st);
         });
     }
     for (int i = 1; i < k.nconv; ++i) {
@@ -981,18 +998,13 @@ void suta_engine::forward(int B) {
             gemm(g);
             timed(F_NORM, [&] {
                 const bool pln = cpl && i + 1 < k.nconv;
-                launch_layernorm_fwd(zbf ? nullptr : pl.z[i], P + o_cg[i], P + o_cbeta[i], Pn, pl.Lc[i],
-                                     pln ? nullptr : pl.a[i], pl.cxhat[i], pl.crstd[i], B * pl.Lc[i], k.C[i], 1e-5f, 1, st,
-                                     pln ? conv_act_plane(i) : nullptr, pl.cmean[i], zbf ? pl.z[i] : nullptr);
+                ln_forward(conv_ln(i), {conv_z(i), pln ? ln_plane(conv_act_plane(i)) : ln_out(pl.a[i])}, st);
             });
         }
     }
     const int C6 = k.C[k.nconv - 1];
     const float* feat = pl.a[k.nconv - 1];
-    timed(F_NORM, [&] {
-        launch_layernorm_fwd(feat, P + o_fpg, P + o_fpb, Pn, T, pl.fp_y, pl.fp_xhat, pl.fp_rstd, (int)BT, C6, k.eps, 0,
-                             st, nullptr, pl.fp_mean);
-    });
+    timed(F_NORM, [&] { ln_forward(feat_proj_ln(), {ln_f32(feat), ln_out(pl.fp_y)}, st); });
     {  // projection (per-utterance trainable W, b)
         GemmParams g = per_utt(T, H, C6, utt(pl.fp_y, C6, (long)T * C6), 0, utt(P + o_pw, C6, Pn), 1, utt(pl.h0, H, (long)T * H));
         add_bias(g, P + o_pb, 0, Pn);
@@ -1029,12 +1041,7 @@ void suta_engine::forward(int B) {
         });
     else
         gemm(posconv_gemm(pl.h0, wpos_f, k.posK / 2, pl.e, pl.h0, bpos, pl.pz));
-    if (!k.stable) {
-        timed(F_NORM, [&] {
-            launch_layernorm_fwd(pl.e, P + o_eg, P + o_eb, Pn, T, pl.enc_y, pl.enc_xhat, pl.enc_rstd, (int)BT, H,
-                                 k.eps, 0, st, plane(0), pl.enc_mean);
-        });
-    }
+    if (!k.stable) timed(F_NORM, [&] { ln_forward(encoder_ln(), {ln_f32(pl.e), ln_out(pl.enc_y, plane(0))}, st); });
     const float scale = 1.0f / std::sqrt((float)d);
     // bf16 mode: producers of the linears' A operands also write bf16 planes (P0 / P1, ping-pong)
     void* P0 = plane(0);
@@ -1045,10 +1052,7 @@ void suta_engine::forward(int B) {
         LayerBufs& lb = pl.lay[l];
         const float* attn_in = lb.x_in;
         if (k.stable) {
-            timed(F_NORM, [&] {
-                launch_layernorm_fwd(lb.x_in, P + o_l1g[l], P + o_l1b[l], Pn, T, dead ? nullptr : lb.y1, lb.xhat1,
-                                     lb.rstd1, (int)BT, H, k.eps, 0, st, P0, lb.mean1);
-            });
+            timed(F_NORM, [&] { ln_forward(layer_ln(l, 1), {ln_f32(lb.x_in), ln_out(dead ? nullptr : lb.y1, P0)}, st); });
             attn_in = dead ? nullptr : lb.y1;  // (dead: the QKV GEMM reads the LN1 plane only)
         }
         void* qkvp = qkv_plane(l);  // the flash kernels' operands
@@ -1087,18 +1091,12 @@ void suta_engine::forward(int B) {
         const float* ffn_res;
         float* ffn_out;
         if (k.stable) {
-            timed(F_NORM, [&] {
-                launch_layernorm_fwd(lb.hmid, P + o_l2g[l], P + o_l2b[l], Pn, T, dead ? nullptr : lb.y2, lb.xhat2,
-                                     lb.rstd2, (int)BT, H, k.eps, 0, st, P0, lb.mean2);
-            });
+            timed(F_NORM, [&] { ln_forward(layer_ln(l, 2), {ln_f32(lb.hmid), ln_out(dead ? nullptr : lb.y2, P0)}, st); });
             ffn_in = dead ? nullptr : lb.y2;
             ffn_res = lb.hmid;
             ffn_out = k.A > 0 ? lb.ad_in : lb.x_out;  // (the adapter kernel writes x_out)
         } else {
-            timed(F_NORM, [&] {
-                launch_layernorm_fwd(pl.rtmp, P + o_l1g[l], P + o_l1b[l], Pn, T, lb.y1, lb.xhat1, lb.rstd1, (int)BT, H,
-                                     k.eps, 0, st, P0);
-            });
+            timed(F_NORM, [&] { ln_forward(layer_ln(l, 1), {ln_f32(pl.rtmp), ln_out(lb.y1, P0)}, st); });
             ffn_in = lb.y1;
             ffn_res = lb.y1;
             ffn_out = pl.rtmp;
@@ -1123,19 +1121,11 @@ void suta_engine::forward(int B) {
                 launch_adapter_fwd(lb.ad_in, P + o_adg[l], P + o_adb[l], Pn, T, B, H, adw[l], 1e-5f, lb.x_out, lb.ad_mean,
                                    lb.ad_rstd, st);
             });
-        if (!k.stable) {
-            timed(F_NORM, [&] {
-                launch_layernorm_fwd(pl.rtmp, P + o_l2g[l], P + o_l2b[l], Pn, T, lb.x_out, lb.xhat2, lb.rstd2, (int)BT,
-                                     H, k.eps, 0, st, P0);
-            });
-        }
+        if (!k.stable) timed(F_NORM, [&] { ln_forward(layer_ln(l, 2), {ln_f32(pl.rtmp), ln_out(lb.x_out, P0)}, st); });
     }
     const float* hfin = pl.lay[k.L - 1].x_out;
     if (k.stable) {
-        timed(F_NORM, [&] {
-            launch_layernorm_fwd(hfin, P + o_eg, P + o_eb, Pn, T, dead ? nullptr : pl.enc_y, pl.enc_xhat, pl.enc_rstd,
-                                 (int)BT, H, k.eps, 0, st, P0, pl.enc_mean);
-        });
+        timed(F_NORM, [&] { ln_forward(encoder_ln(), {ln_f32(hfin), ln_out(dead ? nullptr : pl.enc_y, P0)}, st); });
         hfin = dead ? nullptr : pl.enc_y;
     }
     {  // lm_head
@@ -1193,8 +1183,7 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
     float* t2 = pl.d3;
     if (k.stable) {
         timed(F_NORM, [&] {
-            launch_layernorm_bwd(dx, pl.enc_xhat, pl.enc_rstd, P + o_eg, P + o_eb, Pn, T, B, H, 0, nullptr, nullptr, t1,
-                                 G + o_eg, G + o_eb, Pn, pl.lnpart, st, P0, pl.lay[k.L - 1].x_out, pl.enc_mean);
+            ln_backward(encoder_ln(), ln_bwd(ln_f32(dx), ln_out(t1, P0), ln_f32(pl.lay[k.L - 1].x_out)), st);
         });
         std::swap(dx, t1);
     }
@@ -1203,10 +1192,7 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
         float* dhres;  // grad flowing into the attention-block output (residual point)
         if (!k.stable) {
             // dr2 = LN2 bwd(dx)
-            timed(F_NORM, [&] {
-                launch_layernorm_bwd(dx, lb.xhat2, lb.rstd2, P + o_l2g[l], P + o_l2b[l], Pn, T, B, H, 0, nullptr,
-                                     nullptr, t1, G + o_l2g[l], G + o_l2b[l], Pn, pl.lnpart, st, P0);
-            });
+            timed(F_NORM, [&] { ln_backward(layer_ln(l, 2), ln_bwd(ln_f32(dx), ln_out(t1, P0)), st); });
             // du = (dr2 @ W2) * gelu'(u)
             du_gemm(t1, l);
             {  // dh1 = du @ W1 + dr2
@@ -1215,10 +1201,7 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
                 gemm(g);
             }
             // dr1 = LN1 bwd(dh1)
-            timed(F_NORM, [&] {
-                launch_layernorm_bwd(t2, lb.xhat1, lb.rstd1, P + o_l1g[l], P + o_l1b[l], Pn, T, B, H, 0, nullptr,
-                                     nullptr, t1, G + o_l1g[l], G + o_l1b[l], Pn, pl.lnpart, st, P0);
-            });
+            timed(F_NORM, [&] { ln_backward(layer_ln(l, 1), ln_bwd(ln_f32(t2), ln_out(t1, P0)), st); });
             dhres = t1;  // dr1
         } else {
             if (k.A > 0) {  // through the adapter first: dh = dx + adapter-bwd(dx) (its plane P0 for du_gemm)
@@ -1233,9 +1216,7 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
             void* dyp = dy_planes() ? plane(2) : nullptr;  // (plane 2's dctx of the layer above is consumed)
             gemm(linear(du32, P1, w1[l], 0, dyp ? nullptr : t2, dyp, (int)BT, H, k.F));
             timed(F_NORM, [&] {
-                launch_layernorm_bwd(dyp ? nullptr : t2, lb.xhat2, lb.rstd2, P + o_l2g[l], P + o_l2b[l], Pn, T, B, H, 0,
-                                     nullptr, dx, t1, G + o_l2g[l], G + o_l2b[l], Pn, pl.lnpart, st, P0, lb.hmid,
-                                     lb.mean2, dyp);
+                ln_backward(layer_ln(l, 2), ln_bwd(dyp ? ln_bf16(dyp) : ln_f32(t2), ln_out(t1, P0), ln_f32(lb.hmid), dx), st);
             });
             dhres = t1;  // dhmid
         }
@@ -1305,9 +1286,7 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
             void* dyp = (dy_planes() && dqkvp) ? plane(2) : nullptr;
             gemm(linear(dqkv32, dqkvp, wqkv[l], 0, dyp ? nullptr : t2, dyp, (int)BT, H, 3 * H));
             timed(F_NORM, [&] {
-                launch_layernorm_bwd(dyp ? nullptr : t2, lb.xhat1, lb.rstd1, P + o_l1g[l], P + o_l1b[l], Pn, T, B, H, 0,
-                                     nullptr, dhres, dx, G + o_l1g[l], G + o_l1b[l], Pn, pl.lnpart, st, P0, lb.x_in,
-                                     lb.mean1, dyp);
+                ln_backward(layer_ln(l, 1), ln_bwd(dyp ? ln_bf16(dyp) : ln_f32(t2), ln_out(dx, P0), ln_f32(lb.x_in), dhres), st);
             });
             // dx now holds grad wrt x_in; t1/t2 free
         }
@@ -1315,10 +1294,7 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
     // encoder input
     float* de = dx;
     if (!k.stable) {
-        timed(F_NORM, [&] {
-            launch_layernorm_bwd(dx, pl.enc_xhat, pl.enc_rstd, P + o_eg, P + o_eb, Pn, T, B, H, 0, nullptr, nullptr, t1,
-                                 G + o_eg, G + o_eb, Pn, pl.lnpart, st, nullptr, pl.e, pl.enc_mean);
-        });
+        timed(F_NORM, [&] { ln_backward(encoder_ln(), ln_bwd(ln_f32(dx), ln_out(t1), ln_f32(pl.e)), st); });
         de = t1;
     }
     // dpz, dh0: the two of d1, d2, d3 that de does not occupy, in cyclic order after de (checked against the nested
@@ -1379,42 +1355,34 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
     // feature-projection LN bwd; in group mode also * gelu'(z_last) => dz_last
     float* cur = pl.dzc2;
     timed(F_NORM, [&] {
-        launch_layernorm_bwd(pl.dzc, pl.fp_xhat, pl.fp_rstd, P + o_fpg, P + o_fpb, Pn, T, B, C6, 0,
-                             (!k.layer_mode && hp.train_feature) ? pl.z[last] : nullptr, nullptr, cur, G + o_fpg,
-                             G + o_fpb, Pn, pl.lnpart, st, nullptr, pl.a[last], pl.fp_mean);
+        LnBwd b = ln_bwd(ln_f32(pl.dzc), ln_out(cur), ln_f32(pl.a[last]));
+        if (!k.layer_mode && hp.train_feature) b.post_aux = pl.z[last];
+        ln_backward(feat_proj_ln(), b, st);
     });
     if (!hp.train_feature) return;
     float* other = pl.dzc;
     // bf16 conv storage: z_i and (below the last layer) da_i are bf16 planes in place in their fp32 buffers
     const bool zbf = k.layer_mode && conv_z_bf16();
+    auto conv_dy = [&](int i) { return zbf && i < last ? ln_bf16(cur) : ln_f32(cur); };  // cur = da_i
     for (int i = last; i >= 1; --i) {
         // cur: group mode -> dz_i ; layer mode -> da_i
-        bool bias_done = false;
+        bool fused = false;  // the LayerNorm backward also sums the conv bias gradient (one read of dz_i)
         const bool cpl = conv_planes();
         if (k.layer_mode) {
-            timed(F_NORM, [&] {
-                // fused: the LayerNorm backward also sums the conv bias gradient (one read of dz_i)
-                const int bfin = zbf ? (2 | (i < last ? 1 : 0)) : 0;
-                if (!pl.cxhat[i] && (fused_conv_ln() || cpl) &&
-                    layernorm_bwd_conv_part_floats(B, pl.Lc[i], k.C[i], 0) <= pl.lnpart_floats &&
-                    launch_layernorm_bwd_conv(cur, pl.crstd[i], P + o_cg[i], P + o_cbeta[i], Pn, pl.Lc[i], B, k.C[i],
-                                              // both conv GEMMs read dz_i from its plane: no fp32 copy
-                                              cpl && conv_dx_planes() ? nullptr : other, G + o_cg[i], G + o_cbeta[i],
-                                              k.conv_bias ? G + o_cb[i] : nullptr,
-                                              nullptr, Pn, pl.lnpart, st, pl.z[i], pl.cmean[i], nullptr, 0, 0, 0,
-                                              cpl ? conv_dz_plane() : nullptr, bfin)) {
-                    bias_done = true;
-                } else if (zbf) {
-                    throw SutaError(SUTA_ERR_UNSUPPORTED, "conv stack in bf16: the fused LayerNorm backward is required");
-                } else {
-                    launch_layernorm_bwd(cur, pl.cxhat[i], pl.crstd[i], P + o_cg[i], P + o_cbeta[i], Pn, pl.Lc[i], B,
-                                         k.C[i], 1, nullptr, nullptr, other, G + o_cg[i], G + o_cbeta[i], Pn, pl.lnpart,
-                                         st, nullptr, pl.z[i], pl.cmean[i]);
-                }
-            });
+            const LnConvGrads cg{k.conv_bias ? G + o_cb[i] : nullptr};  // (no weight gradient: a GEMM below)
+            float* dz32 = cpl && conv_dx_planes() ? nullptr : other;  // both conv GEMMs read dz_i's plane: no fp32 copy
+            LnBwd b = ln_bwd(conv_dy(i), ln_out(dz32, cpl ? conv_dz_plane() : nullptr), conv_z(i));
+            b.conv = &cg;
+            fused = (fused_conv_ln() || cpl) && ln_bwd_route(conv_ln(i), b).sums_conv_grads;
+            if (!fused) {  // the plain backward; launch_colsum follows (only the fused one writes the dz plane)
+                if (zbf) throw SutaError(SUTA_ERR_UNSUPPORTED, "conv stack in bf16: the fused LayerNorm backward is required");
+                if (cpl) throw SutaError(SUTA_ERR_UNSUPPORTED, "conv planes: dz plane not written");
+                b = ln_bwd(ln_f32(cur), ln_out(other), ln_f32(pl.z[i]));
+            }
+            timed(F_NORM, [&] { ln_backward(conv_ln(i), b, st); });
             std::swap(cur, other);
         }
-        if (k.conv_bias && !bias_done)
+        if (k.conv_bias && !fused)
             timed(F_NORM, [&] { launch_colsum(cur, B, pl.Lc[i], k.C[i], G + o_cb[i], Pn, pl.lnpart, st); });
         {  // dW_i = im2col(a_{i-1})^T dz_i
             GemmParams g = per_utt(k.K[i] * k.C[i - 1], k.C[i], pl.Lc[i],
@@ -1422,7 +1390,6 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
                                    utt(cur, k.C[i], (long)pl.Lc[i] * k.C[i]), 0, utt(G + o_cw[i], k.C[i], Pn));
             if (cpl) {  // bf16 planes: the forward's activation plane and the LayerNorm-written dz plane (the fp32
                         // activation was not stored)
-                if (!bias_done) throw SutaError(SUTA_ERR_UNSUPPORTED, "conv planes: dz plane not written");
                 g.A = nullptr;
                 set_planes(g, conv_act_plane(i - 1), g.lda, conv_dz_plane(), g.ldb);
             }
@@ -1450,7 +1417,6 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
                 if (zprev) set_aux(g, EPI_DGELU, utt(zprev + (long)rho * Cin, (long)S_ * Cin, (long)Lin * Cin));
                 if (cpl && conv_dx_planes()) {  // bf16 planes: the LayerNorm-written dz plane and the forward's
                                                 // source-layout bf16 weights (strides in bf16 elements)
-                    if (!bias_done) throw SutaError(SUTA_ERR_UNSUPPORTED, "conv planes: dz plane not written");
                     g.A = nullptr;
                     g.B = nullptr;
                     set_planes(g, conv_dz_plane(), Cout, static_cast<char*>(conv_wt_plane(i, 1)) + tap0 * 2, Cout);
@@ -1475,25 +1441,17 @@ void suta_engine::backward(int B, const suta_hparams& hp) {
         }, 4.0 * B * ((double)pl.N + (double)pl.Lc[0] * k.C[0]));  // waveform and activation gradient read
         return;
     }
-    bool fused0 = false;
-    timed(F_NORM, [&] {
-        // fused: the LayerNorm backward also sums the conv0 bias and weight gradients (dz0 read once)
-        if (!pl.cxhat[0] && (fused_conv_ln() || zbf) && k.K[0] == 10 &&
-            layernorm_bwd_conv_part_floats(B, pl.Lc[0], k.C[0], 10) <= pl.lnpart_floats &&
-            // dz0 itself is consumed in registers (conv0's bias and weight gradients): not stored
-            launch_layernorm_bwd_conv(cur, pl.crstd[0], P + o_cg[0], P + o_cbeta[0], Pn, pl.Lc[0], B, k.C[0], nullptr,
-                                      G + o_cg[0], G + o_cbeta[0], k.conv_bias ? G + o_cb[0] : nullptr, G + o_cw[0], Pn,
-                                      pl.lnpart, st, pl.z[0], pl.cmean[0], pl.x, pl.N, k.S[0], 10, nullptr,
-                                      zbf ? (2 | (last > 0 ? 1 : 0)) : 0)) {
-            fused0 = true;
-        } else if (zbf) {
-            throw SutaError(SUTA_ERR_UNSUPPORTED, "conv stack in bf16: the fused conv0 LayerNorm backward is required");
-        } else {
-            launch_layernorm_bwd(cur, pl.cxhat[0], pl.crstd[0], P + o_cg[0], P + o_cbeta[0], Pn, pl.Lc[0], B, k.C[0], 1,
-                                 nullptr, nullptr, other, G + o_cg[0], G + o_cbeta[0], Pn, pl.lnpart, st, nullptr,
-                                 pl.z[0], pl.cmean[0]);
-        }
-    });
+    // fused: the LayerNorm backward also sums the conv0 bias and weight gradients (dz0 read once, consumed in
+    // registers: not stored)
+    const LnConvGrads cg{k.conv_bias ? G + o_cb[0] : nullptr, G + o_cw[0], pl.x, pl.N, k.S[0], k.K[0]};
+    LnBwd b = ln_bwd(conv_dy(0), LnOut{}, conv_z(0));
+    b.conv = &cg;
+    const bool fused0 = (fused_conv_ln() || zbf) && ln_bwd_route(conv_ln(0), b).sums_conv_grads;
+    if (!fused0) {
+        if (zbf) throw SutaError(SUTA_ERR_UNSUPPORTED, "conv stack in bf16: the fused conv0 LayerNorm backward is required");
+        b = ln_bwd(ln_f32(cur), ln_out(other), ln_f32(pl.z[0]));
+    }
+    timed(F_NORM, [&] { ln_backward(conv_ln(0), b, st); });
     if (fused0) return;
     if (k.conv_bias)
         timed(F_NORM, [&] { launch_colsum(other, B, pl.Lc[0], k.C[0], G + o_cb[0], Pn, pl.lnpart, st); });

@@ -1,5 +1,5 @@
 // Non-GEMM kernels of the SUTA step for gfx950: waveform normalisation, conv0 stencil,
-// GroupNorm / LayerNorm forward+backward with per-utterance affine gradients, attention
+// GroupNorm forward+backward with per-utterance affine gradients (LayerNorm: norm.hip), attention
 // softmax forward/backward, the fused entropy+MCC loss-and-grad, and AdamW with
 // duplicate-entry multiplicity.  All reductions are fixed-order (bitwise reproducible).
 #include "ops.h"
@@ -87,18 +87,6 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ x,
     }
 }
 
-typedef __bf16 lnbf16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 load_bf16x4(const __bf16* src) {  // one 8-B load, exact widening
-    const lnbf16x4 b = *reinterpret_cast<const lnbf16x4*>(src);
-    return f32x4{(float)b[0], (float)b[1], (float)b[2], (float)b[3]};
-}
-__device__ __forceinline__ void store_bf16x4(__bf16* dst, f32x4 v) {  // RNE, one 8-B store
-    lnbf16x4 b;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) b[e] = (__bf16)v[e];
-    *reinterpret_cast<lnbf16x4*>(dst) = b;
-}
-
 // Vectorised form (layer-norm conv stack: conv0 output stored): a thread owns 4 consecutive channels
 // (C / 4 threads per frame, 256 / (C / 4) frames per pass), taps KT / stride ST compile-time, 16-B stores;
 // per-element arithmetic and order as conv0_kernel.  Requires C % 4 == 0 and 256 % (C / 4) == 0.
@@ -146,7 +134,6 @@ __global__ __launch_bounds__(256) void conv0_vec_kernel(const float* __restrict_
 // ------------------------------------------------------------------------------------------
 // per-utterance column statistics (GroupNorm with groups == channels), double partials
 // ------------------------------------------------------------------------------------------
-constexpr int CS_ROWS = 128;
 __global__ __launch_bounds__(256) void col_stats_final(const double* __restrict__ part, int nchunk, int rows, int C,
                                                        float eps, float* __restrict__ mean, float* __restrict__ rstd,
                                                        const int* __restrict__ rows_b) {
@@ -305,641 +292,6 @@ __global__ __launch_bounds__(256) void conv0_dw_reduce(const float* __restrict__
     dW[(long)b * gstride + i] = (float)s;
 }
 
-
-// ------------------------------------------------------------------------------------------
-// LayerNorm over D (<= 2048): one wave per row
-// ------------------------------------------------------------------------------------------
-template <int NPL>  // elements per lane = ceil(D / 64)
-__global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ g,
-                                                            const float* __restrict__ beta, long pstride,
-                                                            int rows_per_utt, float* __restrict__ y,
-                                                            float* __restrict__ xhat, float* __restrict__ rstd,
-                                                            int rows, int D, float eps, int gelu_out,
-                                                            float* __restrict__ meanp) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int u = (int)(row / rows_per_utt);
-    const float* xr = x + row * D;
-    float v[NPL];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) {
-        const int c = lane + i * 64;
-        v[i] = c < D ? xr[c] : 0.f;
-        s += v[i];
-    }
-    s = wave_sum(s);
-    const float mean = s / D;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) {
-        const int c = lane + i * 64;
-        const float d = c < D ? v[i] - mean : 0.f;
-        q += d * d;
-    }
-    q = wave_sum(q);
-    const float rs = 1.0f / sqrtf(q / D + eps);
-    const float* gu = g + (long)u * pstride;
-    const float* bu = beta + (long)u * pstride;
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) {
-        const int c = lane + i * 64;
-        if (c < D) {
-            const float xh = (v[i] - mean) * rs;
-            if (xhat) xhat[row * D + c] = xh;
-            const float o = xh * gu[c] + bu[c];
-            y[row * D + c] = gelu_out ? gelu_f(o) : o;
-        }
-    }
-    if (lane == 0) {
-        rstd[row] = rs;
-        if (meanp) meanp[row] = mean;
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// data2vec-audio positional stack: LayerNorm(no affine) -> GELU over D (<= 2048), one wave per row, the layout of
-// layernorm_fwd_kernel.  Rows at or past the utterance's length (tlen, may be null) are written as 0 in both
-// directions, so the next layer's conv sees zero padding there and no gradient leaves them.
-//   fwd: a = gelu(xhat) (+ resid: the stack's last layer adds the stack's input), mean and rstd stored
-//   bwd: dy = da * gelu'(xhat), dz = rstd * (dy - mean(dy) - xhat * mean(dy * xhat)); xhat recomputed from z
-// ------------------------------------------------------------------------------------------
-template <int NPL>
-__global__ __launch_bounds__(256) void ln_gelu_fwd_kernel(const float* __restrict__ z, const float* __restrict__ resid,
-                                                          float* __restrict__ a, float* __restrict__ meanp,
-                                                          float* __restrict__ rstd, int rows, int rows_per_utt, int D,
-                                                          float eps, const int* __restrict__ tlen) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int u = (int)(row / rows_per_utt);
-    const bool valid = !tlen || (int)(row - (long)u * rows_per_utt) < tlen[u];
-    const float* zr = z + row * D;
-    float v[NPL];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) {
-        const int c = lane + i * 64;
-        v[i] = (valid && c < D) ? zr[c] : 0.f;
-        s += v[i];
-    }
-    s = wave_sum(s);
-    const float mean = s / D;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) {
-        const int c = lane + i * 64;
-        const float d = c < D ? v[i] - mean : 0.f;
-        q += d * d;
-    }
-    q = wave_sum(q);
-    const float rs = 1.0f / sqrtf(q / D + eps);
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) {
-        const int c = lane + i * 64;
-        if (c < D) {
-            float o = valid ? gelu_f((v[i] - mean) * rs) : 0.f;
-            if (resid) o += resid[row * D + c];
-            a[row * D + c] = o;
-        }
-    }
-    if (lane == 0) {
-        rstd[row] = rs;
-        meanp[row] = mean;
-    }
-}
-
-template <int NPL>
-__global__ __launch_bounds__(256) void ln_gelu_bwd_kernel(const float* __restrict__ da, const float* __restrict__ z,
-                                                          const float* __restrict__ meanp,
-                                                          const float* __restrict__ rstd, float* __restrict__ dz,
-                                                          int rows, int rows_per_utt, int D,
-                                                          const int* __restrict__ tlen) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int u = (int)(row / rows_per_utt);
-    const bool valid = !tlen || (int)(row - (long)u * rows_per_utt) < tlen[u];
-    if (!valid) {
-        for (int c = lane; c < D; c += 64) dz[row * D + c] = 0.f;
-        return;
-    }
-    const float mean = meanp[row], rs = rstd[row];
-    float xh[NPL], dy[NPL];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) {  // all loads first; columns past D hold xhat = 0, dy = 0
-        const int c = lane + i * 64;
-        xh[i] = c < D ? z[row * D + c] : mean;
-        dy[i] = c < D ? da[row * D + c] : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) {
-        xh[i] = (xh[i] - mean) * rs;
-        dy[i] *= dgelu_f(xh[i]);
-        s1 += dy[i];
-        s2 += dy[i] * xh[i];
-        // erff's polynomial takes ~20 registers per element in flight: without the fence the scheduler interleaves
-        // all NPL of them (176 VGPRs at NPL = 16, scratch at 32)
-        if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-    }
-    s1 = wave_sum(s1) / D;
-    s2 = wave_sum(s2) / D;
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) {
-        const int c = lane + i * 64;
-        if (c < D) dz[row * D + c] = rs * (dy[i] - s1 - xh[i] * s2);
-    }
-}
-
-constexpr int LNB_ROWS = 16;
-template <int NPL>
-__global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ xhat,
-                                                            const float* __restrict__ rstd, const float* __restrict__ g,
-                                                            const float* __restrict__ beta, long pstride,
-                                                            int rows_per_utt, int D, int gelu_in,
-                                                            const float* __restrict__ post_aux,
-                                                            const float* __restrict__ resid, float* __restrict__ dx,
-                                                            float* __restrict__ part, int nchunk,
-                                                            const float* __restrict__ xin,
-                                                            const float* __restrict__ meanp) {
-    // the block's gamma / beta partials cross LDS; D > 1024 (NPL = 32) does the two in turn through one plane
-    // (both planes at once would be the whole 64 KB of static LDS)
-    constexpr int RP = NPL <= 16 ? 2 : 1;
-    __shared__ float red[4][RP][NPL * 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int u = blockIdx.y, ch = blockIdx.x;
-    const float* gu = g + (long)u * pstride;
-    const float* bu = beta + (long)u * pstride;
-    float gam[NPL], bet[NPL];
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) {
-        const int c = lane + i * 64;
-        gam[i] = c < D ? gu[c] : 0.f;
-        bet[i] = c < D ? bu[c] : 0.f;
-    }
-    float pg[NPL], pb[NPL];
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) pg[i] = pb[i] = 0.f;
-    const int r0 = ch * LNB_ROWS, r1 = min(rows_per_utt, r0 + LNB_ROWS);
-    for (int r = r0 + w; r < r1; r += 4) {
-        const long row = (long)u * rows_per_utt + r;
-        float gi[NPL], xh[NPL];
-        float s1 = 0.f, s2 = 0.f;
-        const float rs = rstd[row];
-        const float mu = xhat ? 0.f : meanp[row];
-#pragma unroll
-        for (int i = 0; i < NPL; ++i) {
-            const int c = lane + i * 64;
-            if (c < D) {
-                xh[i] = xhat ? xhat[row * D + c] : (xin[row * D + c] - mu) * rs;  // recomputed: bitwise the fwd x-hat
-                float d = dy[row * D + c];
-                if (gelu_in) d *= dgelu_f(xh[i] * gam[i] + bet[i]);
-                gi[i] = d;
-                pg[i] += d * xh[i];
-                pb[i] += d;
-                const float dg = d * gam[i];
-                s1 += dg;
-                s2 += dg * xh[i];
-            } else {
-                xh[i] = gi[i] = 0.f;
-            }
-        }
-        s1 = wave_sum(s1);
-        s2 = wave_sum(s2);
-        const float m1 = s1 / D, m2 = s2 / D;
-#pragma unroll
-        for (int i = 0; i < NPL; ++i) {
-            const int c = lane + i * 64;
-            if (c < D) {
-                float o = rs * (gi[i] * gam[i] - m1 - xh[i] * m2);
-                if (post_aux) o *= dgelu_f(post_aux[row * D + c]);
-                if (resid) o += resid[row * D + c];
-                dx[row * D + c] = o;
-            }
-        }
-    }
-    if (part) {
-        float* pp = part + ((long)u * nchunk + ch) * 2 * D;
-        if constexpr (RP == 2) {
-#pragma unroll
-            for (int i = 0; i < NPL; ++i) {
-                red[w][0][lane + i * 64] = pg[i];
-                red[w][1][lane + i * 64] = pb[i];
-            }
-            __syncthreads();
-            for (int c = threadIdx.x; c < D; c += 256) {
-                pp[c] = red[0][0][c] + red[1][0][c] + red[2][0][c] + red[3][0][c];
-                pp[D + c] = red[0][1][c] + red[1][1][c] + red[2][1][c] + red[3][1][c];
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NPL; ++i) red[w][0][lane + i * 64] = pg[i];
-            __syncthreads();
-            for (int c = threadIdx.x; c < D; c += 256) pp[c] = red[0][0][c] + red[1][0][c] + red[2][0][c] + red[3][0][c];
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < NPL; ++i) red[w][0][lane + i * 64] = pb[i];
-            __syncthreads();
-            for (int c = threadIdx.x; c < D; c += 256)
-                pp[D + c] = red[0][0][c] + red[1][0][c] + red[2][0][c] + red[3][0][c];
-        }
-    }
-}
-
-// Vectorised LayerNorm forward for D = 256 * NV: one wave per row, lane l owns the 16-B column
-// groups l + 64 i.  gamma / beta are read as scalars (their offsets in the flat parameter buffer need
-// not be 16-B aligned).
-// RPW rows per wave (the bf16-input conv-stack instantiation): every row's loads are issued before the first row's
-// reductions, RPW x the bytes in flight per wave (a 1-KB bf16 row per wave kept the conv LayerNorms latency-bound)
-// FG (bf16-input conv-stack instantiations, SUTA_FAST_GELU): the output GELU by the packed A&S form of the bf16-plane
-// GEMM epilogues (common.h gelu2_bf16ep) instead of erff
-template <int NV, bool GV, bool XB = false, int RPW = 1, bool FG = false>  // XB: x is a bf16 plane (widened exactly)
-__global__ __launch_bounds__(256) void layernorm_fwd_vec_kernel(const float* __restrict__ x,
-                                                                const float* __restrict__ g,
-                                                                const float* __restrict__ beta, long pstride,
-                                                                int rows_per_utt, float* __restrict__ y,
-                                                                float* __restrict__ xhat, float* __restrict__ rstd,
-                                                                int rows, float eps, int gelu_out,
-                                                                __bf16* __restrict__ yb, float* __restrict__ meanp) {
-    constexpr int D = 256 * NV;
-    const int lane = threadIdx.x & 63;
-    const long row0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW;
-    f32x4 vv[RPW][NV];
-#pragma unroll
-    for (int j = 0; j < RPW; ++j) {
-        const long rj = min(row0 + j, (long)rows - 1);
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            if constexpr (XB) vv[j][i] = load_bf16x4(reinterpret_cast<const __bf16*>(x) + rj * D + 4 * (lane + 64 * i));
-            else vv[j][i] = reinterpret_cast<const f32x4*>(x + rj * D)[lane + 64 * i];
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < RPW; ++j) {
-    const long row = row0 + j;
-    if (row >= rows) return;
-    const int u = (int)(row / rows_per_utt);
-    f32x4 v[NV];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        v[i] = vv[j][i];
-        s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-    }
-    s = wave_sum(s);
-    const float mean = s / D;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float d = v[i][e] - mean;
-            q += d * d;
-        }
-    q = wave_sum(q);
-    const float rs = 1.0f / sqrtf(q / D + eps);
-    const float* gu = g + (long)u * pstride;
-    const float* bu = beta + (long)u * pstride;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = 4 * (lane + 64 * i);
-        f32x4 xh, o, gg, bb;
-        if constexpr (GV) {  // 16-B aligned gamma / beta (the launcher checks): one load each per 4 columns
-            gg = *reinterpret_cast<const f32x4*>(gu + c);
-            bb = *reinterpret_cast<const f32x4*>(bu + c);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                gg[e] = gu[c + e];
-                bb[e] = bu[c + e];
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            xh[e] = (v[i][e] - mean) * rs;
-            const float t = xh[e] * gg[e] + bb[e];
-            o[e] = (gelu_out && !FG) ? gelu_f(t) : t;
-        }
-        if (FG && gelu_out) {
-#pragma unroll
-            for (int e = 0; e < 4; e += 2) {
-                const f32x2v g2 = gelu2_bf16ep(f32x2v{o[e], o[e + 1]});
-                o[e] = g2.x;
-                o[e + 1] = g2.y;
-            }
-        }
-        if (xhat) reinterpret_cast<f32x4*>(xhat + row * D)[lane + 64 * i] = xh;
-        if (y) reinterpret_cast<f32x4*>(y + row * D)[lane + 64 * i] = o;  // null: only the bf16 plane is read
-        if (yb) store_bf16x4(yb + row * D + c, o);  // the bf16 plane of the next GEMM's A operand
-    }
-    if (lane == 0) {
-        rstd[row] = rs;
-        if (meanp) meanp[row] = mean;
-    }
-    }
-}
-
-// Vectorised LayerNorm backward for D = 256 * NV: lane l owns the 16-B column groups l + 64 i
-// (i < NV) of every row, so every row access is a fully coalesced 1-KiB wave load.  Same arithmetic,
-// order and partial layout as layernorm_bwd_kernel.  DYB: dy is a bf16 plane (the input gradient of the linear
-// the LayerNorm feeds, written by that GEMM in bf16 only -- torch autocast's bf16 matmul gradient), widened
-// exactly on load.
-template <int NV, bool GV, bool DYB = false>
-__global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(
-    const float* __restrict__ dy, const float* __restrict__ xhat, const float* __restrict__ rstd,
-    const float* __restrict__ g, const float* __restrict__ beta, long pstride, int rows_per_utt, int gelu_in,
-    const float* __restrict__ post_aux, const float* __restrict__ resid, float* __restrict__ dx,
-    float* __restrict__ part, int nchunk, __bf16* __restrict__ dxb, const float* __restrict__ xin,
-    const float* __restrict__ meanp) {
-    constexpr int D = 256 * NV;
-    __shared__ f32x4 red[4][2][NV * 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int u = blockIdx.y, ch = blockIdx.x;
-    const float* gu = g + (long)u * pstride;
-    const float* bu = beta + (long)u * pstride;
-    f32x4 gam[NV], bet[NV], pg[NV], pb[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = 4 * (lane + 64 * i);
-        if constexpr (GV) {
-            gam[i] = *reinterpret_cast<const f32x4*>(gu + c);
-            bet[i] = *reinterpret_cast<const f32x4*>(bu + c);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if constexpr (!GV) {
-                gam[i][e] = gu[c + e];
-                bet[i][e] = bu[c + e];
-            }
-            pg[i][e] = pb[i][e] = 0.f;
-        }
-    }
-    const int r0 = ch * LNB_ROWS, r1 = min(rows_per_utt, r0 + LNB_ROWS);
-    for (int r = r0 + w; r < r1; r += 4) {
-        const long row = (long)u * rows_per_utt + r;
-        const f32x4* xr = reinterpret_cast<const f32x4*>((xhat ? xhat : xin) + row * D);
-        const f32x4* dr = reinterpret_cast<const f32x4*>(dy + row * D);
-        f32x4 gi[NV], xh[NV], pa[NV], rr[NV];
-        float s1 = 0.f, s2 = 0.f;
-        const float rs = rstd[row];
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            xh[i] = xr[lane + 64 * i];
-            if constexpr (DYB) gi[i] = load_bf16x4(reinterpret_cast<const __bf16*>(dy) + row * D + 4 * (lane + 64 * i));
-            else gi[i] = dr[lane + 64 * i];
-        }
-        // every load of the row in flight together (the epilogue operands used to wait behind the reductions)
-        if (post_aux) {
-#pragma unroll
-            for (int i = 0; i < NV; ++i) pa[i] = reinterpret_cast<const f32x4*>(post_aux + row * D)[lane + 64 * i];
-        }
-        if (resid) {
-#pragma unroll
-            for (int i = 0; i < NV; ++i) rr[i] = reinterpret_cast<const f32x4*>(resid + row * D)[lane + 64 * i];
-        }
-        if (!xhat) {  // x-hat recomputed from the LayerNorm input: bitwise the forward's value
-            const float mu = meanp[row];
-#pragma unroll
-            for (int i = 0; i < NV; ++i)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) xh[i][e] = (xh[i][e] - mu) * rs;
-        }
-#pragma unroll
-        for (int i = 0; i < NV; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float d = gi[i][e];
-                if (gelu_in) d *= dgelu_f(xh[i][e] * gam[i][e] + bet[i][e]);
-                gi[i][e] = d;
-                pg[i][e] += d * xh[i][e];
-                pb[i][e] += d;
-                const float dg = d * gam[i][e];
-                s1 += dg;
-                s2 += dg * xh[i][e];
-            }
-        s1 = wave_sum(s1);
-        s2 = wave_sum(s2);
-        const float m1 = s1 / D, m2 = s2 / D;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                o[e] = rs * (gi[i][e] * gam[i][e] - m1 - xh[i][e] * m2);
-                if (post_aux) o[e] *= dgelu_f(pa[i][e]);
-                if (resid) o[e] += rr[i][e];
-            }
-            reinterpret_cast<f32x4*>(dx + row * D)[lane + 64 * i] = o;
-            if (dxb) store_bf16x4(dxb + row * D + 4 * (lane + 64 * i), o);
-        }
-    }
-    if (part) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            red[w][0][lane + i * 64] = pg[i];
-            red[w][1][lane + i * 64] = pb[i];
-        }
-        __syncthreads();
-        f32x4* pp = reinterpret_cast<f32x4*>(part + ((long)u * nchunk + ch) * 2 * D);
-        for (int c = threadIdx.x; c < D / 4; c += 256) {
-            pp[c] = red[0][0][c] + red[1][0][c] + red[2][0][c] + red[3][0][c];
-            pp[D / 4 + c] = red[0][1][c] + red[1][1][c] + red[2][1][c] + red[3][1][c];
-        }
-    }
-}
-
-// Layer-mode conv stack: LayerNorm backward of conv i (D = 512, NV = 2) that also sums what the layer's
-// other two consumers of dz_i read it for -- the conv bias gradient (column sums of dz_i) and, for conv0
-// (KT = kernel taps), the weight gradient dW0[k][c] = sum_t x[S0 t + k] dz0[t][c] -- so dz_i is read once
-// instead of three times (the separate column-sum pass and the conv0 weight-gradient GEMM, 3.4 GB each
-// at 64 x 8 s on wav2vec2-large).  Rows in chunks of CROWS per block (larger chunks for the long layers
-// keep the partial slabs small); partial layout [B][nchunk][2 + 1 + KT][D]: dgamma, dbeta, dbias, dW0 rows;
-// fixed-order reductions (waves, then chunks in order): deterministic.
-// FG (SUTA_FAST_GELU, the bf16-plane instantiations): GELU' by the packed A&S form (common.h dgelu2_bf16ep)
-template <int NV, bool GV, int KT, bool DYB = false, bool XB = false, bool FG = false>  // DYB / XB: dy / x as bf16
-__global__ __launch_bounds__(256) void layernorm_bwd_conv_kernel(
-    const float* __restrict__ dy, const float* __restrict__ rstd, const float* __restrict__ g,
-    const float* __restrict__ beta, long pstride, int rows_per_utt, float* __restrict__ dx, float* __restrict__ part,
-    int nchunk, int crows, const float* __restrict__ xin, const float* __restrict__ meanp,
-    const float* __restrict__ xw, long xws, int xs, __bf16* __restrict__ dxb) {
-    constexpr int D = 256 * NV;
-    constexpr int NVEC = 3 + KT;
-    __shared__ f32x4 red[4][2][NV * 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int u = blockIdx.y, ch = blockIdx.x;
-    const float* gu = g + (long)u * pstride;
-    const float* bu = beta + (long)u * pstride;
-    f32x4 gam[NV], bet[NV], acc[NVEC][NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = 4 * (lane + 64 * i);
-        if constexpr (GV) {
-            gam[i] = *reinterpret_cast<const f32x4*>(gu + c);
-            bet[i] = *reinterpret_cast<const f32x4*>(bu + c);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                gam[i][e] = gu[c + e];
-                bet[i][e] = bu[c + e];
-            }
-        }
-#pragma unroll
-        for (int v = 0; v < NVEC; ++v) acc[v][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    const float* xu = xw ? xw + (long)u * xws : nullptr;
-    const int r0 = ch * crows, r1 = min(rows_per_utt, r0 + crows);
-    for (int r = r0 + w; r < r1; r += 4) {
-        const long row = (long)u * rows_per_utt + r;
-        const f32x4* xr = reinterpret_cast<const f32x4*>(xin + row * D);
-        const f32x4* dr = reinterpret_cast<const f32x4*>(dy + row * D);
-        f32x4 gi[NV], xh[NV];
-        float s1 = 0.f, s2 = 0.f;
-        const float rs = rstd[row];
-        const float mu = meanp[row];
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            if constexpr (XB) xh[i] = load_bf16x4(reinterpret_cast<const __bf16*>(xin) + row * D + 4 * (lane + 64 * i));
-            else xh[i] = xr[lane + 64 * i];
-            if constexpr (DYB) gi[i] = load_bf16x4(reinterpret_cast<const __bf16*>(dy) + row * D + 4 * (lane + 64 * i));
-            else gi[i] = dr[lane + 64 * i];
-        }
-        float xt[KT > 0 ? KT : 1];
-        if constexpr (KT > 0) {
-#pragma unroll
-            for (int k = 0; k < KT; ++k) xt[k] = xu[(long)xs * r + k];
-        }
-#pragma unroll
-        for (int i = 0; i < NV; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) xh[i][e] = (xh[i][e] - mu) * rs;  // x-hat recomputed bitwise
-        if constexpr (FG) {
-#pragma unroll
-            for (int i = 0; i < NV; ++i)
-#pragma unroll
-                for (int e = 0; e < 4; e += 2) {
-                    const f32x2v g2 = dgelu2_bf16ep(f32x2v{xh[i][e] * gam[i][e] + bet[i][e],
-                                                           xh[i][e + 1] * gam[i][e + 1] + bet[i][e + 1]});
-                    gi[i][e] *= g2.x;
-                    gi[i][e + 1] *= g2.y;
-                }
-        }
-#pragma unroll
-        for (int i = 0; i < NV; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float d = FG ? gi[i][e] : gi[i][e] * dgelu_f(xh[i][e] * gam[i][e] + bet[i][e]);
-                gi[i][e] = d;
-                acc[0][i][e] += d * xh[i][e];
-                acc[1][i][e] += d;
-                const float dg = d * gam[i][e];
-                s1 += dg;
-                s2 += dg * xh[i][e];
-            }
-        s1 = wave_sum(s1);
-        s2 = wave_sum(s2);
-        const float m1 = s1 / D, m2 = s2 / D;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = rs * (gi[i][e] * gam[i][e] - m1 - xh[i][e] * m2);
-            if (dx) reinterpret_cast<f32x4*>(dx + row * D)[lane + 64 * i] = o;  // (null: only the plane is read)
-            if (dxb) store_bf16x4(dxb + row * D + 4 * (lane + 64 * i), o);  // the conv GEMMs' bf16 operand plane
-            acc[2][i] += o;
-#pragma unroll
-            for (int k = 0; k < KT; ++k) acc[3 + k][i] += xt[k] * o;
-        }
-    }
-    f32x4* pp = reinterpret_cast<f32x4*>(part + ((long)u * nchunk + ch) * NVEC * D);
-#pragma unroll
-    for (int v = 0; v < NVEC; v += 2) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            red[w][0][lane + i * 64] = acc[v][i];
-            if (v + 1 < NVEC) red[w][1][lane + i * 64] = acc[v + 1][i];
-        }
-        __syncthreads();
-        for (int c = threadIdx.x; c < D / 4; c += 256) {
-            pp[v * (D / 4) + c] = red[0][0][c] + red[1][0][c] + red[2][0][c] + red[3][0][c];
-            if (v + 1 < NVEC) pp[(v + 1) * (D / 4) + c] = red[0][1][c] + red[1][1][c] + red[2][1][c] + red[3][1][c];
-        }
-    }
-}
-
-// chunk sums of layernorm_bwd_conv_kernel's partials in chunk order: vector 0 -> dgamma, 1 -> dbeta,
-// 2 -> dbias (may be null), 3 + k -> dW row k (w_out + k * D)
-__global__ __launch_bounds__(256) void chunk_reduce_conv(const float* __restrict__ part, int nchunk, int nvec, int D,
-                                                         float* __restrict__ dgam, float* __restrict__ dbet,
-                                                         float* __restrict__ dbias, float* __restrict__ wout,
-                                                         long ostride) {
-    const int b = blockIdx.y, v = blockIdx.z;
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= D) return;
-    float* out = v == 0 ? dgam : v == 1 ? dbet : v == 2 ? dbias : (wout ? wout + (long)(v - 3) * D : nullptr);
-    if (!out) return;
-    const float* q = part + ((long)b * nchunk * nvec + v) * D + c;
-    const long cs = (long)nvec * D;
-    float s = 0.f;
-    int chn = 0;
-    for (; chn + 8 <= nchunk; chn += 8) {
-        float t[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) t[k] = q[(chn + k) * cs];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s += t[k];
-    }
-    for (; chn < nchunk; ++chn) s += q[chn * cs];
-    out[(long)b * ostride + c] = s;
-}
-
-// sum partial slabs [B][nchunk][nvec][D] over chunks in order -> out_v[b*ostride + c]
-// (loads issued 8 chunks at a time, summed in chunk order: the result is that of the serial loop)
-__global__ __launch_bounds__(256) void chunk_reduce(const float* __restrict__ part, int nchunk, int nvec, int D,
-                                                    float* __restrict__ out0, float* __restrict__ out1, long ostride) {
-    const int b = blockIdx.y;
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= D) return;
-    for (int v = 0; v < nvec; ++v) {
-        float* out = v == 0 ? out0 : out1;
-        if (!out) continue;
-        const float* q = part + ((long)b * nchunk * nvec + v) * D + c;
-        const long cs = (long)nvec * D;  // chunk stride
-        float s = 0.f;
-        int ch = 0;
-        for (; ch + 8 <= nchunk; ch += 8) {
-            float t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] = q[(ch + u) * cs];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += t[u];
-        }
-        for (; ch < nchunk; ++ch) s += q[ch * cs];
-        out[(long)b * ostride + c] = s;
-    }
-}
-
-__global__ __launch_bounds__(256) void colsum_partial(const float* __restrict__ x, int rows, int C,
-                                                      float* __restrict__ part, int nchunk) {
-    const int b = blockIdx.y, ch = blockIdx.x;
-    const int r0 = ch * CS_ROWS, r1 = min(rows, r0 + CS_ROWS);
-    const float* xb = x + (long)b * rows * C;
-    for (int c = threadIdx.x; c < C; c += 256) {
-        float s = 0.f;
-        int r = r0;
-        for (; r + 8 <= r1; r += 8) {  // 8 loads in flight, summed in row order
-            float t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] = xb[(long)(r + u) * C + c];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += t[u];
-        }
-        for (; r < r1; ++r) s += xb[(long)r * C + c];
-        part[((long)b * nchunk + ch) * C + c] = s;
-    }
-}
 
 // ------------------------------------------------------------------------------------------
 // Grouped positional conv (wav2vec2 pos_conv_embed: K taps, G groups of CG channels, "same" padding)
@@ -1972,196 +1324,6 @@ void launch_conv0(const float* x, long N, const float* W, const float* bias, lon
 
 static int ew_grid(long n) { return (int)std::min<long>(2048, std::max<long>(1, (n + 255) / 256)); }
 
-void launch_layernorm_fwd(const float* x, const float* g, const float* beta, long pstride, int rows_per_utt,
-                          float* y, float* xhat, float* rstd, int rows, int D, float eps, int gelu_out,
-                          hipStream_t st, void* yb_, float* mean, const void* xb) {
-    __bf16* yb = reinterpret_cast<__bf16*>(yb_);
-    if (!xhat && !mean) throw std::runtime_error("layernorm_fwd: x-hat or the row means must be stored");
-    if (xb) {  // bf16 input plane (conv stack on bf16 planes): the vectorised widths, 16-B gamma / beta only
-        auto al = [](const void* q, int a) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; };
-        if (x || !(D == 768 || D == 1024 || D == 512) || !al(xb, 8) || !al(y, 16) || !al(xhat, 16) || !al(g, 16) ||
-            !al(beta, 16) || pstride % 4)
-            throw std::invalid_argument("layernorm_fwd: a bf16 input plane needs the vectorised widths");
-        const float* xp = reinterpret_cast<const float*>(xb);
-        // SUTA_LN_RPW (switch snapshot): rows per wave of the bf16-input (conv stack) forward, 1 or 2; SUTA_FAST_GELU:
-        // the packed A&S GELU (FG)
-        const int rpw = suta_switches().ln_rpw == 2 ? 2 : 1;
-        const bool fg = suta_switches().fast_gelu != 0;
-        const dim3 grid(cdiv(rows, 4 * rpw));
-#define LNFB1(NV_, R_, F_)                                                                                          \
-        hipLaunchKernelGGL((layernorm_fwd_vec_kernel<NV_, true, true, R_, F_>), grid, dim3(256), 0, st, xp, g, beta,    \
-                           pstride, rows_per_utt, y, xhat, rstd, rows, eps, gelu_out, yb, mean)
-#define LNFB(NV_)                                                                                                  \
-        do {                                                                                                       \
-            if (rpw == 2 && fg) LNFB1(NV_, 2, true);                                                               \
-            else if (rpw == 2) LNFB1(NV_, 2, false);                                                               \
-            else if (fg) LNFB1(NV_, 1, true);                                                                      \
-            else LNFB1(NV_, 1, false);                                                                             \
-        } while (0)
-        if (D == 768) LNFB(3);
-        else if (D == 1024) LNFB(4);
-        else LNFB(2);
-#undef LNFB
-#undef LNFB1
-        return;
-    }
-    if (!y && !(yb && (D == 768 || D == 1024 || D == 512)))
-        throw std::runtime_error("layernorm_fwd: the fp32 output may be skipped only beside a bf16 plane");
-    dim3 grid(cdiv(rows, 4));
-    auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const bool vec = a16(x) && a16(y) && (xhat == nullptr || a16(xhat));
-    const bool gv = a16(g) && a16(beta) && pstride % 4 == 0;
-#define LNF(NV_)                                                                                                    \
-    hipLaunchKernelGGL((gv ? layernorm_fwd_vec_kernel<NV_, true> : layernorm_fwd_vec_kernel<NV_, false>), grid,       \
-                       dim3(256), 0, st, x, g, beta, pstride, rows_per_utt, y, xhat, rstd, rows, eps, gelu_out, yb, mean)
-    if (vec && D == 768) LNF(3);
-    else if (vec && D == 1024) LNF(4);
-    else if (vec && D == 512) LNF(2);
-#undef LNF
-    else if (D <= 256)
-        hipLaunchKernelGGL(layernorm_fwd_kernel<4>, grid, dim3(256), 0, st, x, g, beta, pstride, rows_per_utt, y, xhat,
-                           rstd, rows, D, eps, gelu_out, mean);
-    else if (D <= 512)
-        hipLaunchKernelGGL(layernorm_fwd_kernel<8>, grid, dim3(256), 0, st, x, g, beta, pstride, rows_per_utt, y, xhat,
-                           rstd, rows, D, eps, gelu_out, mean);
-    else if (D <= 1024)
-        hipLaunchKernelGGL(layernorm_fwd_kernel<16>, grid, dim3(256), 0, st, x, g, beta, pstride, rows_per_utt, y,
-                           xhat, rstd, rows, D, eps, gelu_out, mean);
-    else if (D <= 2048)  // hidden 1280 / 1920 (XLS-R 1B / 2B)
-        hipLaunchKernelGGL(layernorm_fwd_kernel<32>, grid, dim3(256), 0, st, x, g, beta, pstride, rows_per_utt, y,
-                           xhat, rstd, rows, D, eps, gelu_out, mean);
-    else
-        throw std::invalid_argument("layernorm_fwd: D > 2048");
-    if (yb && !(vec && (D == 768 || D == 1024 || D == 512))) launch_to_bf16(y, D, rows, D, yb, st);
-}
-
-void launch_layernorm_bwd(const float* dy, const float* xhat, const float* rstd, const float* g, const float* beta,
-                          long pstride, int rows_per_utt, int B, int D, int gelu_in, const float* post_aux,
-                          const float* resid, float* dx, float* dgamma, float* dbeta, long gstride, float* part,
-                          hipStream_t st, void* dxb_, const float* x, const float* mean, const void* dyb) {
-    __bf16* dxb = reinterpret_cast<__bf16*>(dxb_);
-    if (!xhat && (!x || !mean)) throw std::runtime_error("layernorm_bwd: x-hat or (x, row means) needed");
-    const int nchunk = cdiv(rows_per_utt, LNB_ROWS);
-    float* pp = (dgamma || dbeta) ? part : nullptr;
-    dim3 grid(nchunk, B);
-    auto a16 = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const bool vec = a16(dy) && a16(xhat) && a16(x) && a16(dx) && a16(post_aux) && a16(resid) && a16(part);
-    const bool gv = a16(g) && a16(beta) && pstride % 4 == 0;
-    if (dyb) {  // bf16 dy plane: the vectorised widths only (the engine's dead-buffer predicate guarantees them)
-        if (dy || !vec || !gv || (reinterpret_cast<uintptr_t>(dyb) & 7) || !(D == 768 || D == 1024 || D == 512))
-            throw std::invalid_argument("layernorm_bwd: a bf16 dy plane needs the vectorised widths and 16-B gamma");
-        const float* dyp = reinterpret_cast<const float*>(dyb);
-#define LNBB(NV_)                                                                                                  \
-        hipLaunchKernelGGL((layernorm_bwd_vec_kernel<NV_, true, true>), grid, dim3(256), 0, st, dyp, xhat, rstd, g, beta, \
-                           pstride, rows_per_utt, gelu_in, post_aux, resid, dx, pp, nchunk, dxb, x, mean)
-        if (D == 768) LNBB(3);
-        else if (D == 1024) LNBB(4);
-        else LNBB(2);
-#undef LNBB
-        if (pp)
-            hipLaunchKernelGGL(chunk_reduce, dim3(cdiv(D, 256), B), dim3(256), 0, st, pp, nchunk, 2, D, dgamma, dbeta,
-                               gstride);
-        return;
-    }
-#define LNB(NV_)                                                                                                   \
-    hipLaunchKernelGGL((gv ? layernorm_bwd_vec_kernel<NV_, true> : layernorm_bwd_vec_kernel<NV_, false>), grid,      \
-                       dim3(256), 0, st, dy, xhat, rstd, g, beta, pstride, rows_per_utt, gelu_in, post_aux, resid, dx, \
-                       pp, nchunk, dxb, x, mean)
-    if (vec && D == 768) LNB(3);
-    else if (vec && D == 1024) LNB(4);
-    else if (vec && D == 512) LNB(2);
-#undef LNB
-    else if (D <= 256)
-        hipLaunchKernelGGL(layernorm_bwd_kernel<4>, grid, dim3(256), 0, st, dy, xhat, rstd, g, beta, pstride,
-                           rows_per_utt, D, gelu_in, post_aux, resid, dx, pp, nchunk, x, mean);
-    else if (D <= 512)
-        hipLaunchKernelGGL(layernorm_bwd_kernel<8>, grid, dim3(256), 0, st, dy, xhat, rstd, g, beta, pstride,
-                           rows_per_utt, D, gelu_in, post_aux, resid, dx, pp, nchunk, x, mean);
-    else if (D <= 1024)
-        hipLaunchKernelGGL(layernorm_bwd_kernel<16>, grid, dim3(256), 0, st, dy, xhat, rstd, g, beta, pstride,
-                           rows_per_utt, D, gelu_in, post_aux, resid, dx, pp, nchunk, x, mean);
-    else if (D <= 2048)
-        hipLaunchKernelGGL(layernorm_bwd_kernel<32>, grid, dim3(256), 0, st, dy, xhat, rstd, g, beta, pstride,
-                           rows_per_utt, D, gelu_in, post_aux, resid, dx, pp, nchunk, x, mean);
-    else
-        throw std::invalid_argument("layernorm_bwd: D > 2048");
-    if (dxb && !(vec && (D == 768 || D == 1024 || D == 512))) launch_to_bf16(dx, D, (long)B * rows_per_utt, D, dxb, st);
-    if (pp)
-        hipLaunchKernelGGL(chunk_reduce, dim3(cdiv(D, 256), B), dim3(256), 0, st, pp, nchunk, 2, D, dgamma, dbeta,
-                           gstride);
-}
-
-long layernorm_bwd_conv_part_floats(int B, int rows_per_utt, int D, int ktaps) {
-    const int crows = rows_per_utt >= 4096 ? 128 : 16;
-    return (long)B * cdiv(rows_per_utt, crows) * (3 + ktaps) * D;
-}
-
-bool launch_layernorm_bwd_conv(const float* dy, const float* rstd, const float* g, const float* beta, long pstride,
-                               int rows_per_utt, int B, int D, float* dx, float* dgamma, float* dbeta, float* dbias,
-                               float* dw, long gstride, float* part, hipStream_t st, const float* x, const float* mean,
-                               const float* xw, long xws, int xs, int ktaps, void* dxb, int bf16_in) {
-    auto a16 = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const bool dyb = bf16_in & 1, xb = bf16_in & 2;  // dy / x given as bf16 planes (8-B aligned suffices)
-    if (D != 512 || !(ktaps == 0 || ktaps == 10) || (ktaps && !xw) || !x || !mean || !dgamma || !dbeta || (!(dx || dxb) && ktaps == 0) ||
-        !((dyb || a16(dy)) && (xb || a16(x)) && a16(dx) && a16(part)))
-        return false;
-    const int crows = rows_per_utt >= 4096 ? 128 : 16;
-    const int nchunk = cdiv(rows_per_utt, crows);
-    const bool gv = a16(g) && a16(beta) && pstride % 4 == 0;
-    const dim3 grid(nchunk, B);
-    if (bf16_in) {  // conv stack on bf16 planes: 16-B gamma / beta (every SUTA layout)
-        if (!gv) return false;
-        const bool fg = suta_switches().fast_gelu != 0;  // SUTA_FAST_GELU: the packed A&S GELU'
-#define LBCB(KT_, DB_, XB_)                                                                                      \
-        do {                                                                                                     \
-            if (fg)                                                                                              \
-                hipLaunchKernelGGL((layernorm_bwd_conv_kernel<2, true, KT_, DB_, XB_, true>), grid, dim3(256), 0, st, dy, \
-                                   rstd, g, beta, pstride, rows_per_utt, dx, part, nchunk, crows, x, mean, xw, xws, \
-                                   xs, reinterpret_cast<__bf16*>(dxb));                                          \
-            else                                                                                                 \
-                hipLaunchKernelGGL((layernorm_bwd_conv_kernel<2, true, KT_, DB_, XB_>), grid, dim3(256), 0, st, dy,   \
-                                   rstd, g, beta, pstride, rows_per_utt, dx, part, nchunk, crows, x, mean, xw, xws, \
-                                   xs, reinterpret_cast<__bf16*>(dxb));                                          \
-        } while (0)
-        if (ktaps == 10) {
-            if (dyb && xb) LBCB(10, true, true);
-            else if (xb) LBCB(10, false, true);
-            else return false;
-        } else {
-            if (dyb && xb) LBCB(0, true, true);
-            else if (xb) LBCB(0, false, true);
-            else return false;
-        }
-#undef LBCB
-        const int nvec = 3 + ktaps;
-        hipLaunchKernelGGL(chunk_reduce_conv, dim3(cdiv(D, 256), B, nvec), dim3(256), 0, st, part, nchunk, nvec, D,
-                           dgamma, dbeta, dbias, dw, gstride);
-        return true;
-    }
-#define LBC(GV_, KT_)                                                                                         \
-    hipLaunchKernelGGL((layernorm_bwd_conv_kernel<2, GV_, KT_>), grid, dim3(256), 0, st, dy, rstd, g, beta, pstride, \
-                       rows_per_utt, dx, part, nchunk, crows, x, mean, xw, xws, xs, reinterpret_cast<__bf16*>(dxb))
-    if (ktaps == 10) {
-        if (gv) LBC(true, 10);
-        else LBC(false, 10);
-    } else {
-        if (gv) LBC(true, 0);
-        else LBC(false, 0);
-    }
-#undef LBC
-    const int nvec = 3 + ktaps;
-    hipLaunchKernelGGL(chunk_reduce_conv, dim3(cdiv(D, 256), B, nvec), dim3(256), 0, st, part, nchunk, nvec, D, dgamma,
-                       dbeta, dbias, dw, gstride);
-    return true;
-}
-
-void launch_colsum(const float* x, int B, int rows, int C, float* out, long ostride, float* part, hipStream_t st) {
-    const int nchunk = cdiv(rows, CS_ROWS);
-    hipLaunchKernelGGL(colsum_partial, dim3(nchunk, B), dim3(256), 0, st, x, rows, C, part, nchunk);
-    hipLaunchKernelGGL(chunk_reduce, dim3(cdiv(C, 256), B), dim3(256), 0, st, part, nchunk, 1, C, out, (float*)nullptr,
-                       ostride);
-}
-
 void launch_softmax_rows(float* s, long nrows, int T, long ld, const int* tlen, long rows_per_utt, hipStream_t st) {
     dim3 grid((unsigned)((nrows + 3) / 4));
     if (T <= 256) hipLaunchKernelGGL(softmax_rows_kernel<4>, grid, dim3(256), 0, st, s, nrows, T, ld, tlen,
@@ -2247,39 +1409,6 @@ bool launch_posconv_stack(bool fwd, const float* x, const float* W, const float*
     // of the backward K - 1 - K / 2; the appended zero taps lie past the last real one in both
     return posconv_launch<true>(fwd, x, W, bias, R, C, nullptr, B, T, H, G, posconv_stack_taps(K),
                                 fwd ? K / 2 : K - 1 - K / 2, tlen, st);
-}
-
-static void ln_gelu_grid(int rows, int D, dim3& grid, int& npl) {
-    grid = dim3((unsigned)((rows + 3) / 4));
-    npl = D <= 256 ? 4 : D <= 512 ? 8 : D <= 1024 ? 16 : 32;
-}
-
-void launch_ln_gelu_fwd(const float* z, const float* resid, float* a, float* mean, float* rstd, int rows,
-                        int rows_per_utt, int D, float eps, const int* tlen, hipStream_t st) {
-    if (D > 2048) throw std::runtime_error("launch_ln_gelu_fwd: D > 2048");
-    dim3 grid;
-    int npl;
-    ln_gelu_grid(rows, D, grid, npl);
-#define LG(N) hipLaunchKernelGGL(ln_gelu_fwd_kernel<N>, grid, dim3(256), 0, st, z, resid, a, mean, rstd, rows, rows_per_utt, D, eps, tlen)
-    if (npl == 4) LG(4);
-    else if (npl == 8) LG(8);
-    else if (npl == 16) LG(16);
-    else LG(32);
-#undef LG
-}
-
-void launch_ln_gelu_bwd(const float* da, const float* z, const float* mean, const float* rstd, float* dz, int rows,
-                        int rows_per_utt, int D, const int* tlen, hipStream_t st) {
-    if (D > 2048) throw std::runtime_error("launch_ln_gelu_bwd: D > 2048");
-    dim3 grid;
-    int npl;
-    ln_gelu_grid(rows, D, grid, npl);
-#define LG(N) hipLaunchKernelGGL(ln_gelu_bwd_kernel<N>, grid, dim3(256), 0, st, da, z, mean, rstd, dz, rows, rows_per_utt, D, tlen)
-    if (npl == 4) LG(4);
-    else if (npl == 8) LG(8);
-    else if (npl == 16) LG(16);
-    else LG(32);
-#undef LG
 }
 
 template <bool FWD>
